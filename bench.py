@@ -69,7 +69,12 @@ def main():
     ap.add_argument("--configs2-world", type=int, default=8, help="world size at which BASELINE configs[2]'s own per-GPU batch is also timed")
     ap.add_argument("--configs2-batch", type=int, default=8)
     ap.add_argument("--dump", default=None, help="directory: every rank writes rank<r>.pt (its final latents, the gathered tensor, a hash of its weights)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="directory: rank 0 writes what the last timed step returned as float32 .npy files (latents.npy; at world > 1 also "
+                         "latents_gathered.npy), so that two builds can be compared output for output on identical seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.emu != (args.backend == "gloo"):
         raise SystemExit("--emu and --backend gloo go together (the product path is RCCL on GPUs)")
 
@@ -188,6 +193,8 @@ def main():
     last = {}
 
     elapsed = timed(dinp, N, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last["lat"], last["gathered"])
     if args.dump:
         import hashlib
         hsh = hashlib.sha256()
@@ -260,6 +267,24 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir: Path, lat, gathered, budget_bytes: int = 60 << 20):
+    """``--dump-outputs``: the final latents of the last timed step (and, at world > 1, the gathered tensor) as float32 ``<name>.npy``.
+    All files together stay under 64 MB: an array larger than its share of the 60 MiB budget is written as a fixed sample instead: the flat elements at the sorted first
+    indices of a ``randperm`` seeded with 0, the same positions in every run of the same shape."""
+    import numpy as np
+    arrays = {"latents": lat}
+    if gathered is not None:
+        arrays["latents_gathered"] = gathered
+    share = budget_bytes // len(arrays)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[: share // 4].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a.numpy())
 
 
 def parity_summary():

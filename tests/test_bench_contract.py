@@ -140,6 +140,45 @@ def test_bench_world2_through_its_own_launcher_on_the_emulator(tmp_path):
         assert torch.equal(s["lat"], r0["gathered"][r:r + 1]), r
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_on_fixed_inputs(tmp_path):
+    """``--dump-outputs DIR``: the final latents of the last timed step as float32 ``latents.npy``.  Two runs with different step counts
+    (the same seeded inputs, every step the same sampling call) write identical arrays; ``steps`` / ``ms_per_step`` follow ``--steps``."""
+    import concurrent.futures as cf
+
+    import numpy as np
+    i = _EMU_FLAGS.index("--steps")
+    base = _EMU_FLAGS[:i] + _EMU_FLAGS[i + 2:]
+    with cf.ThreadPoolExecutor(2) as ex:
+        futs = {k: ex.submit(_run_bench, ["--gpus", "1", *base, "--steps", str(k), "--dump-outputs", str(tmp_path / f"k{k}")]) for k in (1, 2)}
+        lines = {k: f.result() for k, f in futs.items()}
+    for k in (1, 2):
+        assert len(lines[k]) == 1
+        d = json.loads(lines[k][0])
+        assert d["steps"] == k and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["global_batch"] * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        assert sorted(p.name for p in (tmp_path / f"k{k}").iterdir()) == ["latents.npy"]
+    a, b = np.load(tmp_path / "k1" / "latents.npy"), np.load(tmp_path / "k2" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 4, 8, 8) and np.isfinite(a).all() and np.array_equal(a, b)
+
+
+def test_bench_dump_outputs_samples_a_large_output_within_the_budget(tmp_path):
+    """An output over its share of the dump budget (all files under 64 MB) is written as a fixed seeded sample of its elements: the same positions on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+    lat = torch.arange(4 * 4 * 64 * 88, dtype=torch.float32).view(4, 4, 64, 88)
+    bench.dump_outputs(tmp_path / "a", lat, None, budget_bytes=4096)
+    bench.dump_outputs(tmp_path / "b", lat, torch.cat([lat, lat]), budget_bytes=4096)
+    a, b, g = (np.load(tmp_path / p) for p in ("a/latents.npy", "b/latents.npy", "b/latents_gathered.npy"))
+    assert a.dtype == np.float32 and a.shape == (1024,) and b.shape == g.shape == (512,)
+    assert np.all(np.diff(a) > 0) and np.isin(b, a).all() and set(a.tolist()) <= set(lat.flatten().tolist())
+    bench.dump_outputs(tmp_path / "c", lat, None, budget_bytes=4096)
+    assert np.array_equal(a, np.load(tmp_path / "c" / "latents.npy"))
+    bench.dump_outputs(tmp_path / "d", lat, None)
+    assert np.array_equal(np.load(tmp_path / "d" / "latents.npy"), lat.numpy())
+
+
 def test_bench_refuses_the_emulator_without_gloo_and_a_world_mismatch():
     import subprocess
     import sys
