@@ -250,6 +250,14 @@ int pcdm_cfg_step(const float* eps, int cfg, float g, const float* x, const floa
  * then, in place: x <- x', m2 <- m1, m1 <- m_t, last <- x_c (all fp32 [n]; zero m1 / m2 / last before step 0). */
 int pcdm_unipc_step(const float* eps, int cfg, float g, float* x, float* m1, float* m2, float* last, const float* coef,
                     const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+/* CFG combine + DPMSolverMultistepScheduler.step ("DPM++ 2M" and its SDE form; dpmsolver++ / sde-dpmsolver++, solver order <= 2,
+ * midpoint / heun) as one kernel on static state, replayable from a hipGraph.  Row *step_dev of the DEVICE table
+ * coef[step][8] = {a_x, a_e, p_x, p_m0, p_m1, p_z, 0, 0}:
+ *   m0 = a_x x + a_e eps_guided;  x' = p_x x + p_m0 m0 + p_m1 m1 + p_z noise_all[*step_dev][i]
+ * then, in place: x <- x', m1 <- m0 (all fp32 [n]; zero m1 before step 0).  noise_all [steps, n] may be NULL when no row has
+ * p_z != 0 (the term is then skipped).  step_dev NULL: row 0. */
+int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, float* m1, const float* noise_all, const float* coef,
+                    const int32_t* step_dev, int64_t n, pcdm_stream_t s);
 /* Stage-1 prior: CFG combine (src/pipelines/stage1_prior_pipeline.py:467-471) + diffusers
  * UnCLIPScheduler.step (:478-483) + optional affine read-out (post_process_latents, stage1_prior_transformer.py:299-301).
  * pred [2N or N, n/N] fp32 (uncond rows first); HOST coefficients c8 = {p_x, p_e, clip, c_x0, c_x, c_noise, out_scale,

@@ -94,6 +94,7 @@ _SIGS = {
     "pcdm_f32_to_bf16": ([_P, _P, _L, _P], C.c_int),
     "pcdm_cfg_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_unipc_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_dpmpp_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_unclip_step": ([_P, _I, _F, _P, _P, _P, C.POINTER(_F), _L, _P], C.c_int),
     "pcdm_unclip_step_dev": ([_P, _I, _F, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_lincomb": ([_P, _I, C.POINTER(_P), C.POINTER(_F), _L, _P], C.c_int),

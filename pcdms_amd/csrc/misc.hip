@@ -193,6 +193,29 @@ __global__ void unipc_step_kernel(const float* __restrict__ eps, int cfg, float 
     last[i] = xc;
 }
 
+// DPMSolverMultistepScheduler.step (dpmsolver++ / sde-dpmsolver++, order <= 2, midpoint / heun) as ONE elementwise kernel on one
+// static history slot: every variant is linear in (x, eps, m1, noise) with host-known scalars, row *step_dev of a DEVICE table
+// c = {a_x, a_e, p_x, p_m0, p_m1, p_z, 0, 0}:
+//   m0 = a_x x + a_e eps                                        (x0-prediction, convert_model_output)
+//   x' = p_x x + p_m0 m0 + p_m1 m1 + p_z noise_all[*step_dev, i] (noise_all NULL: no noise term)
+// then, in place: x <- x', m1 <- m0.  Every element is owned by one thread.
+__global__ void dpmpp_step_kernel(const float* __restrict__ eps, int cfg, float g, float* __restrict__ x, float* __restrict__ m1,
+                                  const float* __restrict__ noise_all, const float* __restrict__ coef,
+                                  const int32_t* __restrict__ step_dev, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int st = step_dev ? *step_dev : 0;
+    const float* c = coef + 8 * st;
+    float e = eps[i];
+    if (cfg) e = e + g * (eps[n + i] - e);
+    const float xi = x[i];
+    const float m0 = c[0] * xi + c[1] * e;
+    float v = c[2] * xi + c[3] * m0 + c[4] * m1[i];
+    if (noise_all) v += c[5] * noise_all[(int64_t)st * n + i];
+    x[i] = v;
+    m1[i] = m0;
+}
+
 // UnCLIPScheduler.step on a [N, n/N] vector (stage-1 prior): guided prediction -> x0 -> clip -> posterior mean (+ noise),
 // then an optional affine read-out (post_process_latents).  c = {p_x, p_e, clip, c_x0, c_x, c_noise, out_scale, out_shift}.
 struct UnclipArgs { float c[8]; };
@@ -456,6 +479,14 @@ extern "C" int pcdm_unipc_step(const float* eps, int cfg, float g, float* x, flo
                                const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
     if (!eps || !x || !m1 || !m2 || !last || !coef || n <= 0) return -1;
     PCDM_LAUNCH(unipc_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, m2, last, coef, step_dev, n);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, float* m1, const float* noise_all, const float* coef,
+                               const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
+    if (!eps || !x || !m1 || !coef || n <= 0) return -1;
+    PCDM_LAUNCH(dpmpp_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, noise_all, coef, step_dev, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

@@ -864,6 +864,20 @@ def unipc_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torc
                                     _ptr(step_dev), n, _stream(x)), "pcdm_unipc_step")
 
 
+def dpmpp_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torch.Tensor, noise_all: Optional[torch.Tensor],
+               coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None) -> None:
+    """pcdm_dpmpp_step: CFG combine + one DPM-Solver++ step in place on (x, m1); coef fp32 [steps, 8], noise_all fp32
+    [steps, x.numel()] (or None), both on the device."""
+    n = x.numel()
+    for t in (eps, x, m1, coef):
+        _c(t, torch.float32)
+    assert eps.numel() == (2 * n if cfg else n) and m1.numel() == n and coef.shape[-1] == 8
+    if noise_all is not None:
+        assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
+    _chk(_lib.lib().pcdm_dpmpp_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(noise_all), _ptr(coef),
+                                    _ptr(step_dev), n, _stream(x)), "pcdm_dpmpp_step")
+
+
 def unclip_step(pred: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, noise: Optional[torch.Tensor], out: torch.Tensor,
                 coefs: Sequence[float]) -> torch.Tensor:
     """pcdm_unclip_step: coefs = (p_x, p_e, clip, c_x0, c_x, c_noise, out_scale, out_shift); fp32 tensors."""

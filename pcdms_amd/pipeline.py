@@ -6,11 +6,12 @@ conditioning assembly (:430-466), same loop body (:496-519).  Two execution mode
 kernels:
 
 * ``mode="reference"`` -- literally the reference's loop: ``cat`` inputs, ``self.unet(...)``,
-  CFG combine, ``self.scheduler.step(...)`` with any scheduler object (UniPC / DDIM / DDPM).
-* ``mode="fused"`` (default for DDIM with eta = 0 and for UniPC, the shipped driver's scheduler: both are per-step LINEAR
-  updates with host-known coefficients) -- per step: ``pcdm_assemble_input`` -> UNet schedule -> ``pcdm_cfg_step`` /
-  ``pcdm_unipc_step`` (CFG + scheduler update from a device-side coefficient table; UniPC's history lives in static slots)
-  -> ``pcdm_advance_step``; the step is captured once in a hipGraph and replayed ``num_inference_steps`` times (the step
+  CFG combine, ``self.scheduler.step(...)`` with any scheduler object (UniPC / DDIM / DDPM / DPM-Solver++).
+* ``mode="fused"`` (default for DDIM with eta = 0, for UniPC, the shipped driver's scheduler, and for DPM-Solver++ in both its
+  ODE ("DPM++ 2M") and SDE forms: all are per-step LINEAR updates with host-known coefficients; the SDE form's noise is drawn
+  up front into a per-step table) -- per step: ``pcdm_assemble_input`` -> UNet schedule -> ``pcdm_cfg_step`` /
+  ``pcdm_unipc_step`` / ``pcdm_dpmpp_step`` (CFG + scheduler update from a device-side coefficient table; multistep history
+  lives in static slots) -> ``pcdm_advance_step``; the step is captured once in a hipGraph and replayed ``num_inference_steps`` times (the step
   index lives in device memory), which removes ~700 host launches per step from the critical path.
 
 VAE encode/decode are outside the hot path: pass ``masked_latents``
@@ -25,7 +26,7 @@ from typing import Any, Callable, List, Optional, Union
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, DDPMScheduler, UniPCMultistepScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, _step_noise
 from .unet import Stage2_InapintUNet2DConditionModel
 
 
@@ -225,9 +226,11 @@ class Stage2_InpaintDiffusionPipeline:
             and not isinstance(self.scheduler, DDPMScheduler)
         # UniPC (ref stage2_batchtest_inpaint_model.py:132): multistep, but still one linear map per step on static state slots
         linear = linear or (isinstance(self.scheduler, UniPCMultistepScheduler) and self.scheduler.config.solver_order <= 2)
+        # DPM-Solver++ (ODE and SDE form): linear in (x, eps, m1, noise); the SDE noise comes from a per-call table of the same draws
+        linear = linear or isinstance(self.scheduler, DPMSolverMultistepScheduler)
         mode = mode or ("fused" if linear else "reference")
         if mode == "fused" and not linear:
-            raise ValueError("mode='fused' needs a scheduler with one deterministic linear update per step (DDIM with eta=0, UniPC)")
+            raise ValueError("mode='fused' needs a scheduler with one linear update per step (DDIM with eta=0, UniPC, DPM-Solver++)")
 
         if mode == "reference":
             # the literal loop: bare unet(...) calls.  The UNet recognises the step-invariant tensors by identity (it keeps
@@ -254,7 +257,8 @@ class Stage2_InpaintDiffusionPipeline:
         else:
             lat = self._run_fused(lat, mask, masked, pose_cond, feature_f, prior_embed, timesteps, do_cfg,
                                   float(guidance_scale), eta, use_graph, callback, callback_steps,
-                                  float(guidance_rescale) if do_cfg else 0.0, zero_uncond, shared_halves and do_cfg)
+                                  float(guidance_rescale) if do_cfg else 0.0, zero_uncond, shared_halves and do_cfg,
+                                  generator=extra.get("generator"))
 
         return lat
 
@@ -291,6 +295,8 @@ class Stage2_InpaintDiffusionPipeline:
             cfg, g, e = False, 1.0, st["eps_g"]
         if st["unipc"]:
             ops.unipc_step(e, cfg, g, st["lat"], st["m1"], st["m2"], st["last"], st["coef"], st["step"])
+        elif st["dpm"]:
+            ops.dpmpp_step(e, cfg, g, st["lat"], st["m1"], st["noise"], st["coef"], st["step"])
         else:
             ops.cfg_step(e, cfg, g, st["lat"], st["lat"], st["coef"], st["step"])
         ops.advance_step(st["step"])
@@ -300,9 +306,11 @@ class Stage2_InpaintDiffusionPipeline:
         if st.get("unipc"):
             for k in ("m1", "m2", "last"):
                 st[k].zero_()
+        elif st.get("dpm"):
+            st["m1"].zero_()
 
     def _run_fused(self, lat, mask, masked, pose_cond, feature_f, prior_embed, timesteps, do_cfg, g, eta, use_graph,
-                   callback, callback_steps, guidance_rescale=0.0, zero_uncond=False, shared_halves=False):
+                   callback, callback_steps, guidance_rescale=0.0, zero_uncond=False, shared_halves=False, generator=None):
         unet, dev = self.unet, self.device
         if unet._w is None:
             unet._pack()
@@ -312,19 +320,24 @@ class Stage2_InpaintDiffusionPipeline:
         B = rep * N
         n0 = N if (do_cfg and zero_uncond) else 0
         unipc = isinstance(self.scheduler, UniPCMultistepScheduler)
+        dpm = isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        sde = dpm and self.scheduler.stochastic
+        kind = "unipc" if unipc else ("dpm_sde" if sde else "dpm") if dpm else "linear"
         key = (B, h, w, n, rep, n0, tuple(feature_f.shape), None if mask is None else tuple(mask.shape), tuple(masked.shape),
-               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, unipc, bool(shared_halves))
+               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, kind, bool(shared_halves))
         st = self._st if self._graph_key == key else {}
         if not st:
-            st.update(B=B, h=h, w=w, rep=rep, unipc=unipc,
+            st.update(B=B, h=h, w=w, rep=rep, unipc=unipc, dpm=dpm, noise=None,
                       lat=torch.empty_like(lat), mask=None if mask is None else torch.empty_like(mask), masked=torch.empty_like(masked),
                       eps_g=torch.empty_like(lat),
                       x_in=torch.empty(B, h, w, 64, dtype=ops.BF16, device=dev),
                       step=torch.zeros(1, dtype=torch.int32, device=dev),
                       timesteps=torch.empty(n, dtype=torch.int64, device=dev),
-                      coef=torch.empty(n, 12 if unipc else 4, dtype=torch.float32, device=dev))
+                      coef=torch.empty(n, 12 if unipc else 8 if dpm else 4, dtype=torch.float32, device=dev))
             if unipc:   # UniPC history (two stored x0-predictions, last corrected sample): static slots, zeroed per call
                 st.update(m1=torch.zeros_like(lat), m2=torch.zeros_like(lat), last=torch.zeros_like(lat))
+            if dpm:     # DPM-Solver++ history (the previous x0-prediction) and, for the SDE form, the per-step noise table [n, numel]
+                st.update(m1=torch.zeros_like(lat), noise=torch.empty(n, lat.numel(), dtype=torch.float32, device=dev) if sde else None)
             self._graph = None
         # Per call: the static input slots the captured step reads are refilled, and the step-invariant conditioning (class
         # embedding, NHWC pose, the 16 cross-attention K / V^T) is recomputed EAGERLY into the UNet's shape-keyed buffers --
@@ -339,7 +352,10 @@ class Stage2_InpaintDiffusionPipeline:
         # (with the timestep table: the time / class embedding MLPs and every time_emb_proj for ALL steps, once per call)
         st["cond"] = unet.prepare_conditioning(B, h, w, feature_f, prior_embed, pose_cond, zero_ctx_batches=n0, shared_cfg_input=shared_halves,
                                                timesteps=st["timesteps"])
-        st["coef"].copy_(self.scheduler.coefficient_table(device=dev) if unipc else self.scheduler.coefficient_table(eta, device=dev))
+        st["coef"].copy_(self.scheduler.coefficient_table(device=dev) if (unipc or dpm) else self.scheduler.coefficient_table(eta, device=dev))
+        if sde:   # the draws the literal loop would make, one per step in step order, refilled per call outside the captured step
+            for i in range(n):
+                st["noise"][i].copy_(_step_noise(lat.shape, generator, dev).reshape(-1))
         st["g"] = g
         if st.get("gr", guidance_rescale) != guidance_rescale:
             self._graph = None
@@ -462,7 +478,7 @@ class Stage3_RefinedDiffusionPipeline(Stage2_InpaintDiffusionPipeline):
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         lat = self.prepare_latents(s_img_proj_f.shape[0] * N, 4, height, width, torch.float32, device, generator, latents).contiguous()
         extra = self.prepare_extra_step_kwargs(generator, eta)
-        # the same loop machinery as stage 2 (ref :533-563): no mask channel, no pose, no class labels; DDIM / UniPC run as the
+        # the same loop machinery as stage 2 (ref :533-563): no mask channel, no pose, no class labels; DDIM / UniPC / DPM-Solver++ run as the
         # captured fused step, anything else through the literal loop
         lat = self._sample(lat, None, gl, None, feat, None, self.scheduler.timesteps, do_cfg, guidance_scale, guidance_rescale, eta, extra,
                            mode, use_graph, callback, callback_steps, zero_uncond=do_cfg)

@@ -85,6 +85,11 @@ def main():
     pairs = [("ddim", diffusers.DDIMScheduler(**sd21_sched, clip_sample=False, set_alpha_to_one=False, steps_offset=1),
               P.DDIMScheduler(**sd21_sched, clip_sample=False, set_alpha_to_one=False, steps_offset=1), 50),
              ("unipc", diffusers.UniPCMultistepScheduler(**sd21_sched), P.UniPCMultistepScheduler(**sd21_sched), 20),
+             ("dpmpp_2m", diffusers.DPMSolverMultistepScheduler(**sd21_sched), P.DPMSolverMultistepScheduler(**sd21_sched), 20),
+             ("dpmpp_2m_karras", diffusers.DPMSolverMultistepScheduler(**sd21_sched, use_karras_sigmas=True),
+              P.DPMSolverMultistepScheduler(**sd21_sched, use_karras_sigmas=True), 20),
+             ("dpmpp_2m_sde", diffusers.DPMSolverMultistepScheduler(**sd21_sched, algorithm_type="sde-dpmsolver++"),
+              P.DPMSolverMultistepScheduler(**sd21_sched, algorithm_type="sde-dpmsolver++"), 20),
              ("unclip", diffusers.UnCLIPScheduler(**P.UnCLIPScheduler.KANDINSKY22_PRIOR), P.UnCLIPScheduler(**P.UnCLIPScheduler.KANDINSKY22_PRIOR), 20)]
     for name, theirs, ours, n in pairs:
         theirs.set_timesteps(n)
@@ -103,6 +108,9 @@ def main():
                 torch.manual_seed(1234 + i)
                 nt = theirs.step(eps, t, xs_t, prev_timestep=prev).prev_sample
                 no = ours.step(eps.to(dev), t, xs_o.to(dev), prev_timestep=prev, variance_noise=noise.to(dev)).prev_sample
+            elif name == "dpmpp_2m_sde":   # both draw the step's noise from the generator passed: give each the same seed
+                nt = theirs.step(eps, t, xs_t, generator=torch.Generator().manual_seed(1234 + i)).prev_sample
+                no = ours.step(eps.to(dev), t, xs_o.to(dev), generator=torch.Generator().manual_seed(1234 + i)).prev_sample
             else:
                 nt = theirs.step(eps, t, xs_t).prev_sample
                 no = ours.step(eps.to(dev), t, xs_o.to(dev)).prev_sample

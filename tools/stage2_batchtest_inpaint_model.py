@@ -100,7 +100,13 @@ def inference(args, rank, select_test_datas):
         projection_class_embeddings_input_dim=unet_dict["class_embedding.linear_1.weight"].shape[1], torch_dtype=torch.float16,
         low_cpu_mem_usage=False, ignore_mismatched_sizes=True).to(device)
     pipe.unet.load_state_dict(unet_dict)
-    pipe.scheduler = P.UniPCMultistepScheduler.from_config(pipe.scheduler.config)
+    scheduler = getattr(args, "scheduler", "unipc")
+    if scheduler == "unipc":   # the reference driver's choice
+        pipe.scheduler = P.UniPCMultistepScheduler.from_config(pipe.scheduler.config)
+    else:                      # DPM++ 2M, its Karras-sigma and SDE forms
+        pipe.scheduler = P.DPMSolverMultistepScheduler.from_config(
+            pipe.scheduler.config, use_karras_sigmas=scheduler == "dpmpp_2m_karras",
+            algorithm_type="sde-dpmsolver++" if scheduler == "dpmpp_2m_sde" else "dpmsolver++")
     pipe.enable_xformers_memory_efficient_attention()
     print("====================== json_data: {}, model load finish ===================".format(args.json_path.split("/")[-1]))
 
@@ -186,6 +192,7 @@ def build_parser():
     p.add_argument("--img_width", type=int, default=512)
     p.add_argument("--img_height", type=int, default=512)
     p.add_argument("--calculate_metrics", action="store_true")
+    p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p
 
