@@ -171,7 +171,9 @@ typedef struct pcdm_gemm_params {
                                    Upsample2D: conv3x3(nearest-upsample x2 (x)) at output pixel (2y + a, 2x + b) is a 2x2 convolution of x with summed taps, i.e.
                                    one 3x3 launch on the LOW-RES input with N = 4 Cout (group = phase 2a + b, taps {3(a+i) + b + j}), 4/9 of the FLOPs, followed by
                                    pcdm_pixel_shuffle2 (diffusers Upsample2D as composed at stage2_inpaint_unet_2d_condition.py:407-430).  stride 1, no upsample,
-                                   no extra K (a2 / a3), tap_group_n a multiple of the N tile in use (else -1: pick a tile that divides it) */
+                                   no extra K (a2 / a3), tap_group_n a multiple of the N tile in use (else -1: pick a tile that divides it).  Only the
+                                   4 ntaps low bits of each group's 16 are read (higher bits are ignored); every tap id must be <= 8; a group whose ntaps
+                                   taps are all tap 0 is taken for ntaps <= 3 and refused (-1) at ntaps = 4 */
     int32_t tap_group_n;
 } pcdm_gemm_params;
 /* pcdm_version() == 5: the struct above STARTS with struct_size and ends with a3, lda3, tap_lut, tap_group_n (4: ended with rowvec_step_count, step_error; 3: no struct_size, ended with

@@ -178,11 +178,21 @@ extern "C" int pcdm_gemm(const pcdm_gemm_params* p, pcdm_stream_t s) {
         if (p->cin <= 0 || p->cin % BK || p->K != ntaps * p->cin || ntaps < 1 || ntaps > 4 || p->stride != 1 || p->upsample || p->no_pad_lo || p->dup_rows ||
             p->a2 || p->a3 || p->Hi != p->Ho || p->Wi != p->Wo || p->N % p->tap_group_n || p->N / p->tap_group_n > 4 || p->tap_group_n % 64)
             return -1;
-        for (int g = 0; g < p->N / p->tap_group_n; ++g)
+        // each group reads the nibbles of its ntaps taps only (bits above 4 ntaps are ignored).  The kernel takes a group table of 0 as "the
+        // plain nine taps": a group whose taps are all tap 0 is passed with nibble ntaps (never read) set -- at ntaps = 4 there is none: -1
+        uint64_t lut = 0;
+        for (int g = 0; g < p->N / p->tap_group_n; ++g) {
+            uint64_t grp = (p->tap_lut >> (16 * g)) & ((1ull << (4 * ntaps)) - 1);
             for (int t = 0; t < ntaps; ++t)
-                if (((p->tap_lut >> (16 * g + 4 * t)) & 15) > 8 || ((p->tap_lut >> (16 * g)) & 0xffff) == 0) return -1;
+                if (((grp >> (4 * t)) & 15) > 8) return -1;
+            if (grp == 0) {
+                if (ntaps == 4) return -1;
+                grp = 1ull << (4 * ntaps);
+            }
+            lut |= grp << (16 * g);
+        }
         if (p->M != p->B * p->Ho * p->Wo) return -1;
-        a.tap_lut = p->tap_lut;
+        a.tap_lut = lut;
         a.tap_group_n = p->tap_group_n;
     } else if (p->conv) {
         const int cx = p->K - 9 * p->cin;   // extra K behind the nine taps: a 1x1 convolution over a2 [+ a3] at the output pixel (pcdm_gemm_params.a3)

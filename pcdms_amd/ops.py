@@ -25,6 +25,7 @@ BF16 = torch.bfloat16
 LAUNCH_LOG: Optional[list] = None  # set to [] by bench.py to time individual launches with HIP events
 LAUNCH_KEYS: Optional[list] = None  # set to [] by tools/tune_in_step.py: (index into LAUNCH_LOG, tuning-table key) of every table-driven GEMM launch
 LAUNCH_SPANS: Optional[list] = None  # ... and ("ln" key, first, end) = the LAUNCH_LOG entries of every LayerNorm -> Linear pair
+LN_REFUSED: Optional[set] = None   # set to set() by tools/tune_in_step.py: the "ln" keys whose table-named fused call the library refused (-1)
 AUTOTUNE = True                    # pick the GEMM tile configuration per problem shape at first use (GPU only)
 DEFER_SPLITK = os.environ.get("PCDM_DEFER_SPLITK", "1") != "0"   # split-K reduce folded into the consuming GroupNorm (A/B switch)
 
@@ -558,6 +559,8 @@ def _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, ou
             e0.record()
         rc = fused_(choice)
         if rc == -1 and not tile:
+            if LN_REFUSED is not None:
+                LN_REFUSED.add(key)
             two_launches()
             return out
         _chk(rc, "pcdm_gemm (LayerNorm folded)")
