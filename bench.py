@@ -12,7 +12,11 @@ batch=4, 50 DDIM steps, bf16, 1xMI355X").  N>1: every rank samples its own pair 
 per-GPU batch (weak scaling), then ONE RCCL all-gather collects the final latents.  Launched bare
 (``python bench.py --gpus 8``, no WORLD_SIZE in the environment) it spawns the N ranks itself through
 ``torch.distributed.run`` on 127.0.0.1; under an external launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.
-At N=8 it also reports BASELINE.json configs[2]'s own per-GPU batch (8 => 64 images per step) as ``config.configs2``.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write ``--dump-outputs`` and print the line.
+Everything else it can report runs with ``--full`` (each leg can still be dropped with its ``--no-*`` flag): the separate VAE
+encode / decode timing, the per-launch roofline of one eager denoise step, the committed parity summary, the CPU baseline
+(rank 0, N=1) and, at N=8, BASELINE.json configs[2]'s own per-GPU batch (8 => 64 images per step) as ``config.configs2``.
 
 Synthetic data: seeded random-init weights of the full 868.9 M-parameter stage-2
 UNet and seeded synthetic conditioning -- there are no checkpoints / DeepFashion pairs offline.
@@ -52,11 +56,14 @@ def main():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=352, help="single image width; the canvas is 2x this")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the VAE timing, the roofline, the parity summary, the CPU baseline and (at "
+                         "--configs2-world) the configs[2] batch; without it a run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the separate VAE encode/decode timing (SURVEY.md §8f N1)")
-    ap.add_argument("--no-configs2", action="store_true", help="at --gpus 8: skip the extra batch-8-per-GPU (configs[2]) measurement")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-launch roofline")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the separate VAE encode/decode timing (SURVEY.md §8f N1)")
+    ap.add_argument("--no-configs2", action="store_true", help="with --full at --gpus 8: skip the extra batch-8-per-GPU (configs[2]) measurement")
     ap.add_argument("--attn", choices=("bf16", "fp8"), default="bf16",
                     help="fp8 = BASELINE.json configs[4]: e4m3 attention operands on the MX-scaled fp8 MFMA (looser parity; NOT the headline)")
     # ---- crash-proofing of the world > 1 code path where no multi-GPU node exists (tests/test_bench_contract.py; never a measurement):
@@ -230,7 +237,7 @@ def main():
                                  "e2e_frac_executed count what is issued"},
     }
     N8 = args.configs2_batch
-    if world == args.configs2_world and world > 1 and N != N8 and not args.no_configs2:
+    if args.full and world == args.configs2_world and world > 1 and N != N8 and not args.no_configs2:
         # BASELINE.json configs[2] as written: batch 64 over 8 GPUs = 8 images (UNet batch 16) per GPU; same protocol
         inp8 = synth_inputs(cfg, h, w, N8, **synth_kw)
         inp8["latents"] = torch.randn(inp8["latents"].shape, generator=torch.Generator().manual_seed(2000 + rank))
@@ -242,9 +249,9 @@ def main():
             torch.save({"lat": last["lat"].cpu(), "gathered": last["gathered"].cpu()}, Path(args.dump) / f"rank{rank}_configs2.pt")
         timed(dinp, N, 1, 0)   # every rank: back to the headline workload's captured state (kernel_roofline re-runs single steps of it)
 
-    if rank == 0 and not args.no_vae:
+    if args.full and rank == 0 and not args.no_vae:
         result["config"].update(vae_timing(dev, N, args.height, 2 * args.width, ms_per_step))
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         result["roofline"] = kernel_roofline(pipe, ops, dinp, N, h, w)
         # whole-path fraction of the MFMA roof beside the dominant family's (un-hoisted algorithmic FLOPs, see config.flops_note)
         result["roofline"]["e2e_frac"] = round(e2e_tflops / PEAK_BF16_TFLOPS, 4)
@@ -258,9 +265,9 @@ def main():
         ex_tflops = result["roofline"]["executed_gflop_per_denoise_step"] * 1e9 * args.ddim_steps * args.steps / elapsed / 1e12
         result["roofline"]["e2e_frac_executed"] = round(ex_tflops / PEAK_BF16_TFLOPS, 4)
         result["config"]["e2e_tflops_per_gpu_executed"] = round(ex_tflops, 1)
-    if rank == 0:
+    if args.full and rank == 0:
         result["parity"] = parity_summary()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N=1 only (other ranks would idle)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N=1 only (other ranks would idle)
         result["cpu_baseline"] = cpu_baseline(N, args.ddim_steps)
     if use_dist:
         dist.barrier()

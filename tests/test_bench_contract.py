@@ -107,13 +107,13 @@ def test_bench_world2_through_its_own_launcher_on_the_emulator(tmp_path):
     """The code that will run on the 8-GPU node, executed with MORE THAN ONE RANK before the driver does: a bare
     ``python bench.py --gpus 2`` becomes the launcher (no monkeypatch: real ``torch.distributed.run`` children on 127.0.0.1), every rank draws
     its replicated weights with ``device_state_dict``, samples its own pair, the final latents are gathered, the timed region is bracketed by
-    barriers + a MAX all-reduce, and -- with ``--configs2-world 2`` -- the branch that times BASELINE configs[2]'s own per-GPU batch runs too.
+    barriers + a MAX all-reduce, and -- with ``--full --configs2-world 2`` -- the branch that times BASELINE configs[2]'s own per-GPU batch runs too.
     Here the process group is gloo and the kernels are the lane-emulator build of the same sources (tiny UNet, one DDIM step): a plumbing
     test, no measurement.  Checked: ONE JSON line; world size 2 in it; both ranks hold identical weights; the gathered tensor is identical
     on both ranks, and its r-th slice equals a SINGLE-process run of the same file with pair seed 1000 + r (same device-drawn weights)."""
     import torch
     d2 = tmp_path / "w2"
-    lines = _run_bench(["--gpus", "2", *_EMU_FLAGS, "--configs2-world", "2", "--configs2-batch", "2", "--dump", str(d2)])
+    lines = _run_bench(["--gpus", "2", *_EMU_FLAGS, "--full", "--configs2-world", "2", "--configs2-batch", "2", "--dump", str(d2)])
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["rccl_world_size"] == 2 and d["config"]["process_group"] == "gloo" and d["config"]["global_batch"] == 2
@@ -159,6 +159,20 @@ def test_bench_dump_outputs_are_the_last_timed_step_on_fixed_inputs(tmp_path):
         assert sorted(p.name for p in (tmp_path / f"k{k}").iterdir()) == ["latents.npy"]
     a, b = np.load(tmp_path / "k1" / "latents.npy"), np.load(tmp_path / "k2" / "latents.npy")
     assert a.dtype == np.float32 and a.shape == (1, 4, 8, 8) and np.isfinite(a).all() and np.array_equal(a, b)
+
+
+def test_bench_plain_run_reports_the_headline_only():
+    """A plain run prints the headline line and nothing it had to run or read beside the timed steps; ``--full`` adds the other legs
+    (here the parity summary: the VAE, roofline and CPU-baseline legs need a GPU and are switched off)."""
+    i = _EMU_FLAGS.index("--no-cpu-baseline")
+    plain_flags, no_legs = _EMU_FLAGS[:i], _EMU_FLAGS[i:]
+    (plain,) = _run_bench(["--gpus", "1", *plain_flags])
+    (full,) = _run_bench(["--gpus", "1", *plain_flags, "--full", *no_legs])
+    p, f = json.loads(plain), json.loads(full)
+    headline = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"}
+    assert set(p) == headline and p["steps"] == 1 and p["warmup"] == 0 and p["value"] > 0
+    assert not {"vae_encode_ms", "graph_wall_minus_busy_ms", "configs2"} & set(p["config"])
+    assert set(f) == headline | {"parity"} and f["parity"]["oracle"]
 
 
 def test_bench_dump_outputs_samples_a_large_output_within_the_budget(tmp_path):

@@ -6,7 +6,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/${1:-final}
 mkdir -p $OUT
 export TMPDIR=/tmp
-(timeout 400 python bench.py) > $OUT/bench.json 2> $OUT/bench.err
+(timeout 400 python bench.py --full) > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $REPO/bench.py --no-cpu-baseline --no-roofline --no-vae > $OUT/bench_prof.json 2> $OUT/bench_prof.err
 timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python $REPO/tools/profile_step.py > /dev/null 2>&1

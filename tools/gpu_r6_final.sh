@@ -14,7 +14,7 @@ cd $REPO
 python tools/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write $OUT/gemm_traffic.json > $OUT/kernel_traffic.json 2> $OUT/kernel_traffic.err
 rm -rf $OUT/pmc_fetch $OUT/pmc_write
 cp $OUT/gemm_traffic.json profiles/gemm_traffic.json
-(timeout 500 python bench.py) > $OUT/bench.json 2> $OUT/bench.err
+(timeout 500 python bench.py --full) > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $REPO/bench.py --no-cpu-baseline --no-roofline --no-vae > $OUT/bench_prof.json 2> $OUT/bench_prof.err
 cd $REPO
@@ -39,8 +39,8 @@ for x in 0 1; do python tools/pmc_attn_fetch.py $OUT/pmc_attn_fetch_$x > $OUT/at
 (timeout 120 python tools/bench_gn.py 2>&1 | grep -v amdgpu.ids) > $OUT/bench_gn.txt
 (timeout 200 python tools/bench_ln_gemm.py 2>&1 | grep -v amdgpu.ids) > $OUT/bench_ln_gemm.txt
 (timeout 400 python tools/bench_three_stage.py 2>&1 | grep -v amdgpu.ids | tail -3) > $OUT/three_stage.json
-(timeout 300 python bench.py --no-cpu-baseline --no-vae --attn fp8 2>/dev/null) > $OUT/bench_attn_fp8.json
-(timeout 300 python bench.py --no-cpu-baseline --no-vae --batch 8 2>/dev/null) > $OUT/bench_batch8.json
+(timeout 300 python bench.py --full --no-cpu-baseline --no-vae --attn fp8 2>/dev/null) > $OUT/bench_attn_fp8.json
+(timeout 300 python bench.py --full --no-cpu-baseline --no-vae --batch 8 2>/dev/null) > $OUT/bench_batch8.json
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4) > $OUT/gpu_tests.txt
 (timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2) > $OUT/smoke.txt
 cat $OUT/attn_fetch_xcd0.json $OUT/attn_fetch_xcd1.json; cat $OUT/gpu_tests.txt $OUT/smoke.txt

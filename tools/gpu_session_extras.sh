@@ -14,5 +14,5 @@ timeout 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OU
 cd $REPO
 python tools/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write $OUT/gemm_traffic.json > $OUT/kernel_traffic.json 2> $OUT/kernel_traffic.err
 rm -rf $OUT/pmc_fetch $OUT/pmc_write
-(timeout 300 python bench.py --no-cpu-baseline --no-vae) > $OUT/bench_roofline.json 2>/dev/null
+(timeout 300 python bench.py --full --no-cpu-baseline --no-vae) > $OUT/bench_roofline.json 2>/dev/null
 cat $OUT/tests.log; cut -c1-400 $OUT/three_stage.json; for f in bf16 fp8 batch8; do cut -c1-200 $OUT/bench_$f.json; done

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Per-kernel summary of the TIMED region of a rocprofv3 --kernel-trace run of bench.py: the hipGraph replays of the denoise step.
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bench -- python bench.py --no-cpu-baseline --no-roofline
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bench -- python bench.py
     python tools/kernel_trace_summary.py <dir> > profiles/r2_kernel_step_summary.txt
 
-`--stats` aggregates the whole process (weight packing, online tuning of the VAE shapes, warm-up); this script keeps only the last
+`--stats` aggregates the whole process (weight packing, warm-up); this script keeps only the last
 `--steps` denoise steps (delimited by cfg_step_kernel dispatches) and reports, per kernel instantiation, launches per step, average
 duration and time per step -- the numbers bench.py's `roofline.avg_launch_us` (HIP events) must agree with."""
 from __future__ import annotations

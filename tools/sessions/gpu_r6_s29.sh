@@ -5,8 +5,8 @@ OUT=gpurun_out/r6_s29
 mkdir -p $OUT
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4) > $OUT/gpu_tests.txt
 (timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2) > $OUT/smoke.txt
-(timeout 500 python bench.py) > $OUT/bench.json 2> $OUT/bench.err
-(PCDM_PHASE_UPSAMPLE=0 timeout 500 python bench.py --no-cpu-baseline --no-roofline) > $OUT/bench_gather.json 2>/dev/null
+(timeout 500 python bench.py --full) > $OUT/bench.json 2> $OUT/bench.err
+(PCDM_PHASE_UPSAMPLE=0 timeout 500 python bench.py --full --no-cpu-baseline --no-roofline) > $OUT/bench_gather.json 2>/dev/null
 (timeout 400 python tools/bench_three_stage.py 2>&1 | grep -v amdgpu.ids | tail -2) > $OUT/three_stage.json
 cat $OUT/gpu_tests.txt $OUT/smoke.txt
 for f in bench bench_gather; do python - $OUT/$f.json <<'PY'

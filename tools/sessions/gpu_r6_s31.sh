@@ -12,5 +12,5 @@ cd $REPO
 python tools/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write $OUT/gemm_traffic.json > $OUT/kernel_traffic.json 2> $OUT/kernel_traffic.err
 rm -rf $OUT/pmc_fetch $OUT/pmc_write
 cp $OUT/gemm_traffic.json profiles/gemm_traffic.json
-(timeout 500 python bench.py) > $OUT/bench.json 2> $OUT/bench.err
+(timeout 500 python bench.py --full) > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-200 $OUT/bench.json; grep -o '"traffic": [0-9a-z]*' $OUT/bench.json

@@ -1,6 +1,6 @@
 """A/B helper: run a repo script against an alternative build of libpcdm.so.
 
-    python tools/with_lib.py pcdms_amd/lib/libpcdm_old.so bench.py --no-cpu-baseline --no-vae
+    python tools/with_lib.py pcdms_amd/lib/libpcdm_old.so bench.py --full --no-cpu-baseline --no-vae
 """
 import runpy
 import sys
