@@ -210,6 +210,19 @@ int pcdm_quantize_fp8(const void* x, void* y, int64_t rows, int cols, int cols_p
 int pcdm_flash_attn_fp8(const void* q, int64_t ldq, const void* k8, int64_t ldk, const void* vt8, int64_t ldvt, void* o, int64_t ldo,
                         int B, int H, int Lq, int Lk, float scale, float k_descale, float v_descale, float thr_log2, pcdm_stream_t s);
 
+/* ---- Single-head attention for wide heads: the VAE mid-block attention (diffusers Attention, one head of width d = C).
+ *      o = softmax(q k^T * scale) v, fp32 scores, online fp32 softmax, fp32 accumulation, P and o rounded to bf16.
+ *  d  head width: a multiple of 64, 64 <= d <= 512
+ *  q  [B*Lq, ldq]  bf16, columns [0, d)  (e.g. a column view of the PCDM_EPI_SPLIT_VT output, row stride 2d)
+ *  k  [B*Lk, ldk]  bf16, columns [0, d)
+ *  vt [B, d, ldvt] bf16 = V transposed (key index contiguous), as written by PCDM_EPI_SPLIT_VT; columns [Lk, ldvt) are never used
+ *  o  [B*Lq, ldo]  bf16, columns [0, d) written, nothing else
+ *  Any Lq >= 1, Lk >= 1 (keys of a partial tile are masked out of the softmax), the whole batch in one launch, no workspace;
+ *  reruns are bit-identical.  Returns -1 without launching for: a NULL pointer, B, Lq or Lk < 1, d not a multiple of 64 or above 512,
+ *  a row stride that is not a multiple of 8 elements or smaller than d, ldvt < Lk, a pointer not 16-byte aligned, a non-finite scale. */
+int pcdm_attn_wide(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo,
+                   int B, int Lq, int Lk, int d, float scale, pcdm_stream_t s);
+
 /* ---- K12 time / class embedding helpers.
  * pcdm_timestep_embedding: diffusers Timesteps(dim, flip_sin_to_cos, shift) (ref :184,677): out fp32 [B,dim];
  *   t read from DEVICE memory: t_dev[step_dev ? *step_dev : 0] (int64), broadcast over B.

@@ -84,6 +84,7 @@ _SIGS = {
     "pcdm_flash_attn_thr": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _F, _P], C.c_int),
     "pcdm_quantize_fp8": ([_P, _P, _L, _I, _I, _L, _L, _F, _P], C.c_int),
     "pcdm_flash_attn_fp8": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _F, _F, _F, _P], C.c_int),
+    "pcdm_attn_wide": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding": ([_P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding_rows": ([_P, _I, _P, _I, _I, _F, _P], C.c_int),
     "pcdm_time_class_combine": ([_P, _P, _P, _I, _I, _I, _P], C.c_int),

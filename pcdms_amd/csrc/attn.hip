@@ -459,6 +459,198 @@ __global__ __launch_bounds__(256, 3) void flash_attn_fp8_kernel(const u16* __res
             }
     }
 }
+
+// ---- Single-head attention for WIDE heads (64 <= d <= 512, d % 64 == 0): the VAE mid-block attention (one head, d = C = 512).
+// o = softmax(q k^T * scale) v with fp32 scores, an eager online fp32 softmax, fp32 O accumulation, bf16 P and bf16 output.
+//
+// At d = 512 one wave owning 32 query rows over the whole width would need 256 fp32 accumulator registers per lane for O alone, so
+// the work of a key tile is split across the four waves of a workgroup twice:
+//  * workgroup = 4 waves = ONE block of 32 queries; key tiles of WKT = 128 keys.  Grid (ceil(Lq / 32), B): the whole batch in one launch.
+//  * QK^T is split by KEYS: wave w computes the 32 x 32 scores of keys key0 + 32w .. +31, swapped (S^T = K Q^T: a lane holds 16
+//    scores of ONE query, its partner lane^32 the other 16).  Q [32 x d] is staged once per workgroup in LDS and read as the B operand
+//    (ds_read_b128); K is the A operand straight from global memory (each key row is read by exactly one wave: LDS would add no reuse),
+//    one 64-wide d chunk ahead of the MFMAs.
+//  * Softmax: the wave's row maximum (16 in-register fmax + one __shfl_xor(.,32)) goes through LDS; every wave takes the max of the
+//    four partials in the same order, so the running reference m, the rescale factor and P are identical in all waves.  P is rounded
+//    to bf16 and written to LDS [32 queries][128 keys]; each lane keeps its partial row sum (fp32, un-rounded P), combined across
+//    lanes and waves in a fixed order once at the end -- no atomics, reruns are bit-identical.
+//  * PV is split by d SLICES: the d / 32 output fragments of 32 rows (O^T = V^T P^T, A = V^T rows straight from global memory as
+//    EPI_SPLIT_VT writes them, key-contiguous; B = P^T from LDS, shared by all fragments of the tile) are dealt to the waves round
+//    robin: NF = ceil(d / 128) fragments per wave (d = 64: waves 2, 3 idle in PV).  The V^T operands of a tile's first fragment are
+//    requested before the softmax exchange, so their latency hides behind it.
+//  * Tail keys of a partial tile are -inf in the softmax (a zero-filled key would still score 0 and enter the row sum); their K rows are
+//    read clamped to key Lk - 1 and their V^T elements are zeroed (the columns [Lk, ldvt) of V^T may hold anything).  Tail queries read
+//    row Lq - 1 and are not stored.  No workspace: scratch is the fixed LDS below, whatever Lq and Lk are.
+// Budget per lane at NF = 4 (d > 384): O^T 4 x 16, S^T 16, K operands 2 x 4 x 4 (current + next chunk), Q operands 4 x 4, P^T 8 x 4,
+// V^T 8 x 4 registers + addresses: hipcc allocates 241 VGPRs (NF = 3: 223; NF = 2: 168; NF = 1: 150), no spills =>
+// __launch_bounds__(256, 2): two waves per SIMD at d > 256, three below.  LDS per workgroup
+// (sized for d = 512): Q 32 x 520 bf16 = 33,280 B + P 32 x 136 bf16 = 8,704 B + 512 B of row partials = 42,496 B: three workgroups
+// fit in the 160 KiB of a CU, so registers, not LDS, bound the occupancy.
+constexpr int WQB = 32;                 // queries per workgroup
+constexpr int WKT = 128;                // keys per tile (32 per wave)
+constexpr int WDMAX = 512;
+constexpr int WQP = WDMAX + 8;          // u16 pitch of a staged Q row (16-byte padding: rows 4 banks apart)
+constexpr int WPP = WKT + 8;            // u16 pitch of a P row
+struct WideSmem {
+    u16 q[WQB * WQP];
+    u16 p[WQB * WPP];
+    float red[4][WQB];
+};
+
+template <int NF>
+__global__ __launch_bounds__(256, 2) void attn_wide_kernel(const u16* __restrict__ q, int64_t ldq, const u16* __restrict__ k, int64_t ldk,
+                                                         const u16* __restrict__ vt, int64_t ldvt, u16* __restrict__ o, int64_t ldo,
+                                                         int Lq, int Lk, int d, float c /* scale * log2(e) */) {
+    __shared__ __attribute__((aligned(16))) WideSmem sm;
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int b = blockIdx.y, q0 = blockIdx.x * WQB;
+    const int hh = lane >> 5, col = lane & 31;
+    const int nfrag = d >> 5;               // 32-row fragments of O^T
+
+    // ---- stage Q [32 x d] (rows past Lq: row Lq - 1, never stored)
+    {
+        const int cpr = d >> 3;             // 16-byte chunks per row
+        for (int i = t; i < WQB * cpr; i += 256) {
+            const int r = i / cpr, ch = i - r * cpr;
+            const int qr = q0 + r < Lq ? q0 + r : Lq - 1;
+            *(u16x8*)&sm.q[r * WQP + ch * 8] = *(const u16x8*)(q + ((int64_t)b * Lq + qr) * ldq + ch * 8);
+        }
+    }
+    __syncthreads();
+
+    f32x16 oacc[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[f][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;   // per query (identical in all waves) / this lane's partial row sum
+    const u16* qs = &sm.q[col * WQP + 8 * hh];
+    const u16* vb = vt + (int64_t)b * d * ldvt + 8 * hh;
+    const int nkt = (Lk + WKT - 1) / WKT;
+    const int nch = d >> 6;                 // 64-wide d chunks of the QK^T contraction
+
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int key0 = kt * WKT;
+        const bool partial = key0 + WKT > Lk;
+        // ---- S^T = K Q^T for keys key0 + 32 wave .. +31
+        int krow = key0 + wave * 32 + col;
+        if (krow >= Lk) krow = Lk - 1;
+        const u16* kp = k + ((int64_t)b * Lk + krow) * ldk + 8 * hh;
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        u16x8 kc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kc[j] = *(const u16x8*)(kp + 16 * j);
+        for (int ch = 0; ch < nch; ++ch) {
+            u16x8 kn[4];
+            if (ch + 1 < nch) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) kn[j] = *(const u16x8*)(kp + 64 * (ch + 1) + 16 * j);
+            }
+            u16x8 qf[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) qf[j] = *(const u16x8*)(qs + 64 * ch + 16 * j);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = mfma_32x32x16(kc[j], qf[j], s);
+            if (ch + 1 < nch) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) kc[j] = kn[j];
+            }
+        }
+        // ---- V^T operands of this wave's first fragment (latency hidden behind the softmax exchange)
+        auto load_v = [&](int f, u16x8 (&vf)[8]) {
+            const u16* vp = vb + (int64_t)(32 * f + col) * ldvt + key0;
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const int kc0 = key0 + 16 * ks + 8 * hh;
+                if (!partial) {
+                    vf[ks] = *(const u16x8*)(vp + 16 * ks);
+                } else {
+                    // kc0 < Lk <= ldvt with kc0 and ldvt multiples of 8: the whole 16-byte piece lies inside the row
+                    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+                    if (kc0 < Lk) v = *(const u16x8*)(vp + 16 * ks);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (kc0 + e >= Lk) v[e] = 0;
+                    vf[ks] = v;
+                }
+            }
+        };
+        u16x8 vf[8];
+        if (wave < nfrag) load_v(wave, vf);
+        // ---- online softmax (log2 units).  lane: s[r] = score(query col, key key0 + 32 wave + (r & 3) + 8 (r >> 2) + 4 hh)
+        const int kbase = key0 + wave * 32 + 4 * hh;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] *= c;
+            if (partial && kbase + (r & 3) + 8 * (r >> 2) >= Lk) s[r] = -INFINITY;
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        if (hh == 0) sm.red[wave][col] = mx;
+        __syncthreads();                    // row partials visible; every wave is done reading P of the previous tile
+        const float tm = fmaxf(fmaxf(sm.red[0][col], sm.red[1][col]), fmaxf(sm.red[2][col], sm.red[3][col]));
+        const float m_new = fmaxf(m_run, tm);   // finite: every tile holds at least one key < Lk
+        const float alpha = fast_exp2(m_run - m_new);
+        m_run = m_new;
+        float part[4] = {0.f, 0.f, 0.f, 0.f};
+        u16* pw = &sm.p[col * WPP + wave * 32 + 4 * hh];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            u16x4 pv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float p = fast_exp2(s[4 * g + e] - m_new);
+                part[e] += p;
+                pv[e] = f2bf(p);
+            }
+            *(u16x4*)(pw + 8 * g) = pv;
+        }
+        l_run = l_run * alpha + ((part[0] + part[1]) + (part[2] + part[3]));
+        __syncthreads();                    // P of this tile complete; every wave is done reading the row partials
+        // ---- O^T += V^T P^T over this wave's d fragments
+        u16x8 pf[8];
+        const u16* pr = &sm.p[col * WPP + 8 * hh];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) pf[ks] = *(const u16x8*)(pr + 16 * ks);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+            const int f = wave + 4 * i;
+            if (f < nfrag) {
+                if (i > 0) load_v(f, vf);
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) oacc[i] = mfma_32x32x16(vf[ks], pf[ks], oacc[i]);
+            }
+        }
+    }
+    // ---- row sums: lane halves, then the four waves in a fixed order
+    const float l_w = l_run + __shfl_xor(l_run, 32, 64);
+    if (hh == 0) sm.red[wave][col] = l_w;
+    __syncthreads();
+    const float inv = 1.0f / ((sm.red[0][col] + sm.red[1][col]) + (sm.red[2][col] + sm.red[3][col]));
+    if (q0 + col < Lq) {
+        u16* op = o + ((int64_t)b * Lq + q0 + col) * ldo + 4 * hh;
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int f = wave + 4 * i;
+            if (f < nfrag) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    u16x4 ov;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ov[e] = f2bf(oacc[i][4 * g + e] * inv);
+                    *(u16x4*)(op + 32 * f + 8 * g) = ov;
+                }
+            }
+        }
+    }
+}
 }  // namespace
 
 // XCD-aware block placement (attn_block_coords): PCDM_ATTN_XCD=0 in the environment at load time = the plain grid (A/B switch)
@@ -507,4 +699,27 @@ extern "C" int pcdm_flash_attn_thr(const void* q, int64_t ldq, const void* k, in
 extern "C" int pcdm_flash_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                void* o, int64_t ldo, int B, int H, int Lq, int Lk, float scale, pcdm_stream_t s) {
     return pcdm_flash_attn_thr(q, ldq, k, ldk, vt, ldvt, o, ldo, B, H, Lq, Lk, scale, PCDM_ATTN_DEFAULT_THR, s);
+}
+
+extern "C" int pcdm_attn_wide(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo,
+                              int B, int Lq, int Lk, int d, float scale, pcdm_stream_t s) {
+    if (!q || !k || !vt || !o || B <= 0 || Lq <= 0 || Lk <= 0) return -1;
+    if (d < 64 || d > WDMAX || d % 64) return -1;
+    if (ldq % 8 || ldk % 8 || ldvt % 8 || ldo % 8 || ldq < d || ldk < d || ldo < d || ldvt < Lk) return -1;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)o) & 15) != 0) return -1;   // 16-byte operand loads
+    if (!(scale == scale) || scale > 3.0e38f || scale < -3.0e38f) return -1;
+    const dim3 grid((Lq + WQB - 1) / WQB, B);
+    const float c = scale * 1.44269504088896341f;
+#define PCDM_WIDE_LAUNCH(NF)                                                                                                       \
+    PCDM_LAUNCH(PCDM_KERNEL_NAME(attn_wide_kernel<NF>), grid, dim3(256), 0, (hipStream_t)s, (const u16*)q, ldq, (const u16*)k, ldk, \
+                (const u16*)vt, ldvt, (u16*)o, ldo, Lq, Lk, d, c)
+    switch ((d + 127) / 128) {   // O^T fragments per wave
+        case 1: PCDM_WIDE_LAUNCH(1); break;
+        case 2: PCDM_WIDE_LAUNCH(2); break;
+        case 3: PCDM_WIDE_LAUNCH(3); break;
+        default: PCDM_WIDE_LAUNCH(4); break;
+    }
+#undef PCDM_WIDE_LAUNCH
+    PCDM_CHECK_LAUNCH();
+    return 0;
 }

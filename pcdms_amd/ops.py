@@ -738,6 +738,28 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
     return out
 
 
+def attn_wide(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, Lq: int, Lk: int,
+              scale: Optional[float] = None) -> torch.Tensor:
+    """One head of width d = vt.shape[1] (64 <= d <= 512, d % 64 == 0): q [B*Lq, ldq], k [B*Lk, ldk] (views allowed: row stride =
+    .stride(0), columns [0, d) used), vt [B, d, ldvt] with ldvt >= Lk, out [B*Lq, ldo] (columns [0, d) written)."""
+    for t in (q, k, vt, out):
+        assert t.dtype == BF16
+    assert q.stride(1) == 1 and k.stride(1) == 1 and vt.is_contiguous() and vt.dim() == 3 and out.stride(1) == 1
+    d = vt.shape[1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(d)
+    log = LAUNCH_LOG is not None and q.is_cuda
+    if log:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = _lib.lib().pcdm_attn_wide(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out), out.stride(0),
+                                   B, Lq, Lk, d, scale, _stream(q))
+    _chk(rc, "pcdm_attn_wide")
+    if log:
+        e1.record()
+        LAUNCH_LOG.append(("attn_wide_kernel", 4.0 * B * Lq * Lk * d, e0, e1, (B, Lq, Lk, d)))
+    return out
+
+
 FP8 = torch.uint8   # e4m3 bytes (torch.float8_e4m3fn views of these buffers are never computed on by PyTorch)
 
 

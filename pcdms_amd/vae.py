@@ -7,7 +7,7 @@ followed by ``VaeImageProcessor.postprocess`` (:528-532); ``len(self.vae.config.
 factor (:138).  This class mirrors that surface (``from_pretrained`` / ``load_state_dict`` with diffusers key names /
 ``encode`` / ``decode`` / ``config``) and runs on the same HIP kernels as the UNet: implicit-GEMM 3x3 convolutions
 (stride-2 with bottom/right padding for the encoder, nearest-x2 folded in for the decoder), GroupNorm+SiLU, and the
-mid-block single-head d=C attention as two MFMA GEMMs around a row-softmax kernel.  ``quant_conv`` (1x1 after a 3x3) is
+mid-block single-head d=C attention as one fused launch over the whole batch (``pcdm_attn_wide``, any latent size).  ``quant_conv`` (1x1 after a 3x3) is
 folded exactly into ``encoder.conv_out`` at pack time.
 """
 from __future__ import annotations
@@ -258,23 +258,13 @@ class AutoencoderKL(ModuleSurface):
     def _mid(self, m, x, B, H, W):
         """resnet -> single-head attention (d = C) with residual -> resnet."""
         HW, M, C = H * W, B * H * W, m["c"]
-        if HW % 64:
-            raise NotImplementedError("VAE mid-block attention needs (h/8)*(w/8) to be a multiple of 64")
         x = self._resnet(m["r0"], x, B, H, W, "ma")
         n = self._gn(x, B, HW, m["gn"], False, "gn")
         qk = self._buf("qk", (M, 2 * C))
-        vt = self._buf("vt", (B, C, HW), zero=True)
+        vt = self._buf("vt", (B, C, (HW + 7) // 8 * 8), zero=True)   # key pitch padded to 16 bytes
         ops.gemm(n, m["qkv"], qk, rows_per_batch=HW, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * C)
-        at = self._buf("at", (M, C))
-        S = self._buf("S", (HW, HW), torch.float32)
-        P = self._buf("P", (HW, HW))
-        for b in range(B):   # S[q, k] = K Q^T stored transposed in fp32, softmax rows, O = P V
-            q, k = qk[b * HW:(b + 1) * HW, :C], qk[b * HW:(b + 1) * HW, C:]
-            wq = ops.PackedWeight(q, None, HW, C, HW, alg_nk=HW * C)           # "weights" = Q [HW, C] (row stride 2C)
-            ops.gemm(k, wq, S, rows_per_batch=HW, epilogue=ops.EPI_NCHW_F32, w_ld=2 * C)
-            ops.softmax_rows(S, P, C ** -0.5)
-            wv = ops.PackedWeight(vt[b], None, C, HW, C, alg_nk=C * HW)        # "weights" = V^T [C, HW]
-            ops.gemm(P, wv, at[b * HW:(b + 1) * HW])
+        # o = softmax(q k^T / sqrt(C)) v for the whole batch in one launch: no HW x HW scores anywhere
+        at = ops.attn_wide(qk[:, :C], qk[:, C:], vt, self._buf("at", (M, C)), B, HW, HW, C ** -0.5)
         y = ops.gemm(at, m["out"], self._buf("mb", (M, C)), residual=x, res_mod=M)
         return self._resnet(m["r1"], y, B, H, W, "mc")
 
