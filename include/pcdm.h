@@ -306,6 +306,35 @@ int pcdm_advance_step(int32_t* step_dev, pcdm_stream_t s);
  * in[(b, y, x), (2a + bb) C + c].  The second half of the phase-decomposed Upsample2D convolution (pcdm_gemm_params.tap_lut).  C % 8 == 0. */
 int pcdm_pixel_shuffle2(const void* in, void* out, int B, int H, int W, int C, pcdm_stream_t s);
 
+/* ---- Image metrics of the evaluation drivers (stage2_batchtest_inpaint_model.py:203-219, stage3_batchtest_refined_model.py): score the N decoded
+ * samples of a pair against the target on the device and keep the best one, without a host round trip.
+ * Images are NHWC with 3 channels, uint8 (is_f32 = 0) or fp32 (is_f32 = 1; both tensors the same type): cand [N, Hc, Wc, 3], ref [ref_n, Hr, Wr, 3] with
+ * ref_n = 1 (one target for every candidate) or N.  Each comes with a window {x0, y0, W, H} (int32[4], HOST memory) into its own image -- the right
+ * half of a [source | target] canvas is scored against a stand-alone target with no crop copy; the two windows have the same W, H.
+ * Every call returns -1 and writes nothing for: channels != 3, ref_n not 1 or N, a window that leaves its image or differs in size from the other,
+ * N > 65535, a workspace smaller than pcdm_metrics_ws_bytes or not 8-byte aligned, and (pcdm_ssim) sigma whose radius r = int(3.5 sigma + 0.5) is 0 or
+ * above 8, or W < 2r + 1 or H < 2r + 1.
+ * pcdm_metrics_ws_bytes: size of the caller-provided workspace for pcdm_ssim at this sigma (and for pcdm_psnr; sigma <= 0: for pcdm_psnr alone).  The
+ *   workspace holds per-workgroup partial sums only, needs no initialisation, and is added up in a fixed order: reruns are bit-identical.
+ * pcdm_ssim: scores[n] (fp32, device) = skimage.metrics.structural_similarity(ref, cand[n], gaussian_weights=True, sigma=sigma,
+ *   use_sample_covariance=False, channel_axis=2, data_range=R) with R = data_range, or, for data_range < 0, max - min of the candidate's window over
+ *   all channels: separable Gaussian of radius r, weights exp(-(i / sigma)^2 / 2) normalised to 1, five filtered moments per channel, population
+ *   covariances, the map averaged over the interior [r, H - r) x [r, W - r) and the channels (no tap of an averaged pixel leaves the window, so
+ *   pixels outside it never enter).  fp64 accumulation on values centred per image: |score - fp64 skimage| <= 1e-5, and a constant candidate against
+ *   a constant reference (R = 0) is NaN for any constant.  argmax (int32, device; may be NULL) = np.argmax(scores): the first maximum, a NaN ranks
+ *   as the maximum.  Three launches (min / max, tiles, final sum), no host synchronisation.
+ * pcdm_psnr: mse[n] = mean squared difference over the windows (uint8: integer accumulation, exact), psnr[n] = 10 log10(data_range^2 / mse[n]), +inf for
+ *   identical windows; data_range > 0 (255 for uint8 images); either output may be NULL.
+ * pcdm_select_image: out <- the window of cand_u8[*index_dev] (the index read on the device, clamped into [0, N)): normalized = 0: uint8 [H, W, 3];
+ *   normalized = 1: fp32 NCHW [1, 3, H, W] = (x / 255 - 0.5) / 0.5 in fp32 -- transforms.ToTensor() + Normalize([0.5], [0.5]), bit for bit. */
+int64_t pcdm_metrics_ws_bytes(int N, int ref_n, int W, int H, float sigma);
+int pcdm_ssim(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr, const int32_t* ref_win,
+              int channels, int is_f32, float sigma, float data_range, float* scores, int32_t* argmax, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int pcdm_psnr(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr, const int32_t* ref_win,
+              int channels, int is_f32, float data_range, float* mse, float* psnr, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int pcdm_select_image(const void* cand_u8, int N, int Hc, int Wc, const int32_t* win, int channels, const int32_t* index_dev, void* out, int normalized,
+                      pcdm_stream_t s);
+
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host
  * that is not Python: pcdm_unet_create from the topology, pcdm_unet_set_weight / _set_vector with the packed tensors under their

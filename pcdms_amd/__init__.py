@@ -16,5 +16,7 @@ from .vae import AutoencoderKL  # noqa: F401,E402
 from .cond import ControlNetConditioningEmbedding, ImageProjModel_p  # noqa: F401,E402
 from .prior import Stage1_PriorPipeline, Stage1_PriorTransformer  # noqa: F401,E402
 from .encoders import CLIPVisionModelWithProjection, Dinov2Model  # noqa: F401,E402
+from . import metrics  # noqa: F401,E402
+from .metrics import pick_best, psnr, ssim  # noqa: F401,E402
 
 __version__ = "0.1.0"

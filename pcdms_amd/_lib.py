@@ -71,6 +71,7 @@ class UNetConfig(C.Structure):
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
 _SIGS = {
     "pcdm_version": ([], C.c_int),
     "pcdm_is_emulator": ([], C.c_int),
@@ -105,6 +106,10 @@ _SIGS = {
     "pcdm_image_to_uint8": ([_P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_advance_step": ([_P, _P], C.c_int),
     "pcdm_pixel_shuffle2": ([_P, _P, _I, _I, _I, _I, _P], C.c_int),
+    "pcdm_metrics_ws_bytes": ([_I, _I, _I, _I, _F], _L),
+    "pcdm_ssim": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _F, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_psnr": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_select_image": ([_P, _I, _I, _I, _W4, _I, _P, _P, _I, _P], C.c_int),
     "pcdm_unet_create": ([C.POINTER(UNetConfig)], _P),
     "pcdm_unet_destroy": ([_P], None),
     "pcdm_unet_last_error": ([_P], C.c_char_p),

@@ -961,3 +961,56 @@ def softmax_rows(s: torch.Tensor, out: torch.Tensor, scale: float) -> torch.Tens
 
 def advance_step(step_dev: torch.Tensor) -> None:
     _chk(_lib.lib().pcdm_advance_step(_ptr(step_dev), _stream(step_dev)), "pcdm_advance_step")
+
+
+# ------------------------------------------------------------------------------------ image metrics (pcdms_amd/metrics.py is the public surface)
+def _win(w: Sequence[int]):
+    return (C.c_int32 * 4)(*[int(v) for v in w])
+
+
+def _images(cand: torch.Tensor, ref: torch.Tensor) -> int:
+    assert cand.dim() == 4 and ref.dim() == 4 and cand.dtype == ref.dtype and cand.dtype in (torch.uint8, torch.float32), (cand.shape, ref.shape, cand.dtype, ref.dtype)
+    assert cand.is_contiguous() and ref.is_contiguous() and cand.device == ref.device
+    return int(cand.dtype == torch.float32)
+
+
+def metrics_ws_bytes(N: int, ref_n: int, W: int, H: int, sigma: float) -> int:
+    """Workspace bytes of ``ssim`` at this sigma (and of ``psnr``; sigma <= 0: of ``psnr`` alone); -1: the library refuses the problem."""
+    return int(_lib.lib().pcdm_metrics_ws_bytes(N, ref_n, W, H, float(sigma)))
+
+
+def ssim(cand: torch.Tensor, ref: torch.Tensor, cand_win: Sequence[int], ref_win: Sequence[int], scores: torch.Tensor, argmax: Optional[torch.Tensor],
+         ws: torch.Tensor, *, sigma: float = 1.2, data_range: Optional[float] = None) -> torch.Tensor:
+    """cand [N, Hc, Wc, 3], ref [1 | N, Hr, Wr, 3], both uint8 or both fp32; windows (x0, y0, W, H); scores fp32 [N], argmax int32 [1] or None
+    (include/pcdm.h: pcdm_ssim).  data_range None: max - min of each candidate's window."""
+    f32 = _images(cand, ref)
+    _c(scores, torch.float32)
+    if argmax is not None:
+        _c(argmax, torch.int32)
+    _chk(_lib.lib().pcdm_ssim(_ptr(cand), cand.shape[0], cand.shape[1], cand.shape[2], _win(cand_win), _ptr(ref), ref.shape[0], ref.shape[1], ref.shape[2],
+                              _win(ref_win), cand.shape[3], f32, float(sigma), -1.0 if data_range is None else float(data_range), _ptr(scores),
+                              _ptr(argmax), _ptr(ws), ws.numel() * ws.element_size(), _stream(cand)), "pcdm_ssim")
+    return scores
+
+
+def psnr(cand: torch.Tensor, ref: torch.Tensor, cand_win: Sequence[int], ref_win: Sequence[int], mse: Optional[torch.Tensor], out: Optional[torch.Tensor],
+         ws: torch.Tensor, *, data_range: float = 255.0) -> Optional[torch.Tensor]:
+    """mse / out fp32 [N]: mean squared difference and 10 log10(data_range^2 / mse) over the windows (include/pcdm.h: pcdm_psnr)."""
+    f32 = _images(cand, ref)
+    for t in (mse, out):
+        if t is not None:
+            _c(t, torch.float32)
+    _chk(_lib.lib().pcdm_psnr(_ptr(cand), cand.shape[0], cand.shape[1], cand.shape[2], _win(cand_win), _ptr(ref), ref.shape[0], ref.shape[1], ref.shape[2],
+                              _win(ref_win), cand.shape[3], f32, float(data_range), _ptr(mse), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(),
+                              _stream(cand)), "pcdm_psnr")
+    return out
+
+
+def select_image(cand: torch.Tensor, win: Sequence[int], index: torch.Tensor, out: torch.Tensor, normalized: bool) -> torch.Tensor:
+    """out <- the window of cand[index[0]] (uint8 [N, Hc, Wc, 3]; index int32 on the device): uint8 [H, W, 3], or fp32 [1, 3, H, W] =
+    (x / 255 - 0.5) / 0.5 when ``normalized`` (include/pcdm.h: pcdm_select_image)."""
+    assert cand.dim() == 4
+    _c(cand, torch.uint8); _c(index, torch.int32); _c(out, torch.float32 if normalized else torch.uint8)
+    _chk(_lib.lib().pcdm_select_image(_ptr(cand), cand.shape[0], cand.shape[1], cand.shape[2], _win(win), cand.shape[3], _ptr(index), _ptr(out),
+                                      int(normalized), _stream(cand)), "pcdm_select_image")
+    return out

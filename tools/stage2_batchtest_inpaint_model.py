@@ -5,7 +5,8 @@ Same command line, checkpoint layout and outputs as /root/reference/stage2_batch
 loading :95-133, per-pair conditioning :141-186, sampling call :188-200, best-SSIM / grid output :203-232, one process per GPU
 over ``split_list_into_chunks`` :266-285); every model object is the pcdms_amd one, so the whole driver -- encoders, pose
 embedding, VAE, UNet, scheduler -- runs on the MI355X through libpcdm.so.  What stays host-side is what the reference does
-on the host too: PIL resize / canvas pasting, ``CLIPImageProcessor``, PNG writing, SSIM.
+on the host too: PIL resize / canvas pasting, ``CLIPImageProcessor``, PNG writing, SSIM -- unless ``--metrics_device gpu`` is given: then the samples
+stay on the device as uint8, ``pcdms_amd.metrics.pick_best`` scores and selects there, and only the chosen image and the scores come back.
 
 Differences, on purpose: ``--img_width`` is honoured (the reference parses it but reads ``args.img_weigh``); ``ImageProjModel_p``
 takes its sizes from the checkpoint / encoder config instead of the literals 1536 / 768 / 1024 (identical for the published
@@ -53,6 +54,18 @@ def ssim_gaussian(a: np.ndarray, b: np.ndarray, sigma: float = 1.2) -> float:
         s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux ** 2 + uy ** 2 + c1) * (vx + vy + c2))
         vals.append(s[pad:-pad, pad:-pad].mean())
     return float(np.mean(vals))
+
+
+BEST_INDEX_LOG: list = []   # (output name, index of the saved sample) of every --calculate_metrics pair this process scored
+
+
+def pick_best_on_device(images: torch.Tensor, t_img: Image.Image, window=None):
+    """``--metrics_device gpu``: the uint8 NHWC samples stay on the device, the target is uploaded once, pcdms_amd.metrics.pick_best scores the
+    window of every sample and selects the best; only the chosen image, its index and the N scores come back.  Returns
+    (PIL image, index, [scores])."""
+    target = torch.from_numpy(np.array(t_img)).to(images.device)
+    image, index, scores = P.pick_best(images, target, cand_window=window)
+    return Image.fromarray(image.cpu().numpy()), int(index.item()), [float(v) for v in scores.tolist()]
 
 
 def image_grid(imgs, rows, cols):
@@ -140,17 +153,24 @@ def inference(args, rank, select_test_datas):
         else:
             raise ValueError("Check the input JSON file path")
 
+        on_device = args.calculate_metrics and getattr(args, "metrics_device", "host") == "gpu"
         output = pipe(height=H, width=2 * W, guidance_rescale=0.0, vae_image=vae_image, s_img_proj_f=s_img_proj_f, st_pose_f=st_pose_f,
                       pred_t_img_embed=pred_t_img_embed, num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
-                      num_inference_steps=args.num_inference_steps)
+                      num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
         out_name = s_img_path.split("/")[-1].replace(".png", "") + "_to_" + t_img_path.split("/")[-1]
-        if args.calculate_metrics:
+        if on_device:      # the target half of each [source | generated] canvas against the target, scored where the decoder left it
+            best_img, best, ssim_values = pick_best_on_device(output.images, t_img, (W, 0, W, H))
+            all_ssim.append(ssim_values[best])
+            BEST_INDEX_LOG.append((out_name, best))
+            best_img.save(save_dir_metric + out_name)
+        elif args.calculate_metrics:
             ssim_values = []
             for gen_img in output.images:
                 gen = np.array(gen_img.crop((W, 0, 2 * W, H))) * 255.0
                 ssim_values.append(ssim_gaussian(np.array(t_img) * 255.0, gen))
             best = int(np.argmax(ssim_values))
             all_ssim.append(ssim_values[best])
+            BEST_INDEX_LOG.append((out_name, best))
             output.images[best].crop((W, 0, 2 * W, H)).save(save_dir_metric + out_name)
         else:
             vis_pose = Image.new("RGB", (2 * W, H))
@@ -192,6 +212,8 @@ def build_parser():
     p.add_argument("--img_width", type=int, default=512)
     p.add_argument("--img_height", type=int, default=512)
     p.add_argument("--calculate_metrics", action="store_true")
+    p.add_argument("--metrics_device", choices=("host", "gpu"), default="host",
+                   help="where --calculate_metrics scores the samples: host (scipy, as the reference) or gpu (pcdms_amd.metrics.pick_best)")
     p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p

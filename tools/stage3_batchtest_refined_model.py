@@ -28,6 +28,7 @@ _spec = importlib.util.spec_from_file_location("stage2_driver", Path(__file__).r
 _s2 = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_s2)
 to_tensor_normalized, ssim_gaussian, image_grid = _s2.to_tensor_normalized, _s2.ssim_gaussian, _s2.image_grid
+BEST_INDEX_LOG = _s2.BEST_INDEX_LOG
 
 
 def inference(args, rank, select_test_datas):
@@ -72,14 +73,22 @@ def inference(args, rank, select_test_datas):
         pix = clip_image_processor(images=s_img, return_tensors="pt").pixel_values
         s_img_proj_f = image_proj_model_p(image_encoder_p(pix.to(device)).last_hidden_state)
         vae_gen_t_image = to_tensor_normalized(gen_t_img).unsqueeze(0)
+        on_device = args.calculate_metrics and getattr(args, "metrics_device", "host") == "gpu"
         output = pipe(height=H, width=W, guidance_rescale=args.guidance_scale, vae_gen_t_image=vae_gen_t_image, s_img_proj_f=s_img_proj_f,
                       num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
-                      num_inference_steps=args.num_inference_steps)
-        ssim_values = [ssim_gaussian(np.array(t_img), np.array(g)) for g in output.images]
+                      num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
         out_name = s_img_path.split("/")[-1].replace(".png", "") + "_to_" + t_img_path.split("/")[-1]
+        if on_device:      # the whole refined image against the target, scored on the device (tools/stage2_batchtest_inpaint_model.py)
+            best_img, best, ssim_values = _s2.pick_best_on_device(output.images, t_img)
+            all_ssim.append(ssim_values[best])
+            BEST_INDEX_LOG.append((out_name, best))
+            best_img.save(save_dir_metric + out_name)
+            continue
+        ssim_values = [ssim_gaussian(np.array(t_img), np.array(g)) for g in output.images]
         if args.calculate_metrics:
             best = int(np.argmax(ssim_values))
             all_ssim.append(ssim_values[best])
+            BEST_INDEX_LOG.append((out_name, best))
             output.images[best].save(save_dir_metric + out_name)
         else:
             t_pose = load(args.pose_path + data["target_image"].replace(".jpg", "_pose.jpg"))
@@ -115,6 +124,8 @@ def build_parser():
     p.add_argument("--img_width", type=int, default=512)
     p.add_argument("--img_height", type=int, default=512)
     p.add_argument("--calculate_metrics", action="store_true")
+    p.add_argument("--metrics_device", choices=("host", "gpu"), default="host",
+                   help="where --calculate_metrics scores the samples: host (scipy, as the reference) or gpu (pcdms_amd.metrics.pick_best)")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage3_checkpoints/512")
     return p
 
