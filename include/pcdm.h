@@ -335,6 +335,33 @@ int pcdm_psnr(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, 
 int pcdm_select_image(const void* cand_u8, int N, int Hc, int Wc, const int32_t* win, int channels, const int32_t* index_dev, void* out, int normalized,
                       pcdm_stream_t s);
 
+/* ---- Input preparation of the evaluation drivers (stage2_batchtest_inpaint_model.py:135-149: Image.resize((W, H), Image.BICUBIC), the
+ * [source | black] and [source pose | target pose] canvases, ToTensor + Normalize, CLIPImageProcessor) on the device, from the decoded uint8 pixels.
+ * pcdm_resample_u8: Pillow's 8-bit separable resampler.  src uint8 HWC [Hs, Ws, channels] (channels 3 or 1, contiguous) -> the Hd x Wd window at
+ *   pixel (x0, y0) of a uint8 HWC canvas dst with dst_pitch BYTES between rows (dst_pitch >= (x0 + Wd) channels; the caller guarantees that
+ *   y0 + Hd rows exist); bytes outside the window are not touched, so pasting needs no extra launch.  The filter lives in the tables, one per
+ *   axis, int32 in DEVICE memory: xtab = [lo (Wd) | count (Wd) | coeff (Wd * kx)], ytab likewise with Hd, ky.  Output o of an axis is
+ *   clip8((2^21 + sum_{j < count[o]} coeff[o * k + j] * in[lo[o] + j]) >> 22) in 32-bit integers (weights of about 2^22 in sum, pixels <= 255: no
+ *   overflow), the horizontal pass first and rounded to uint8, then the vertical pass over those bytes.  For Pillow's result build a table as
+ *   ImagingResample does: scale = in / out, filterscale = max(scale, 1), support = filter_support * filterscale, center = (o + 0.5) scale,
+ *   lo = max(int(center - support + 0.5), 0), hi = min(int(center + support + 0.5), in), count = hi - lo, w_j = filter((j + lo - center + 0.5) /
+ *   filterscale) normalised to sum 1 in fp64, coeff = int(w 2^22 + 0.5) (w < 0: int(w 2^22 - 0.5)), k = 2 int(ceil(support)) + 1
+ *   (pcdms_amd/preprocess.py).  An axis whose size does not change takes a NULL table and is copied, as Pillow skips it; a NULL table with
+ *   different sizes, or a table with equal sizes, returns -1.  Table entries are clamped into the image on the device, so a wrong table cannot
+ *   cause an access outside src, dst's window or the workspace.
+ *   One launch: a workgroup owns a 32 x 16 output tile, resamples the input rows it needs horizontally into LDS (rows * 32 * channels bytes) and
+ *   runs the vertical pass out of LDS.  When the rows of a tile exceed 24 KiB of LDS (vertical downscales beyond about 15 : 1) the call takes two
+ *   launches through ws (uint8, pcdm_resample_ws_bytes; 0 and NULL otherwise): same bytes.  No atomics, no host synchronisation.
+ * pcdm_u8_to_nchw: out fp32 NCHW [1, channels, H, W] <- (x - mean[c]) / std[c] over the window win = {x0, y0, W, H} (HOST memory) of src,
+ *   mean / std HOST float[channels], every operation in fp32 in this order.  mode 0: x = float(p) / float(scale) -- scale 255, mean = std = 0.5 is
+ *   transforms.ToTensor() + Normalize([0.5], [0.5]) bit for bit; mode 1: x = float(double(p) * scale) -- scale 1 / 255 with the OpenAI mean / std is
+ *   rescale + normalize of transformers' CLIPImageProcessor (numpy backend) bit for bit; the window is its centre crop. */
+int64_t pcdm_resample_ws_bytes(int Hs, int Ws, int Hd, int Wd, int channels, int ky);
+int pcdm_resample_u8(const void* src, int Hs, int Ws, int channels, const int32_t* xtab, int kx, const int32_t* ytab, int ky, void* dst, int Hd, int Wd,
+                     int64_t dst_pitch, int x0, int y0, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int pcdm_u8_to_nchw(const void* src_u8, int Hs, int Ws, int channels, const int32_t* win, int mode, double scale, const float* mean, const float* std_,
+                    float* out, pcdm_stream_t s);
+
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host
  * that is not Python: pcdm_unet_create from the topology, pcdm_unet_set_weight / _set_vector with the packed tensors under their

@@ -18,5 +18,7 @@ from .prior import Stage1_PriorPipeline, Stage1_PriorTransformer  # noqa: F401,E
 from .encoders import CLIPVisionModelWithProjection, Dinov2Model  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
 from .metrics import pick_best, psnr, ssim  # noqa: F401,E402
+from . import preprocess  # noqa: F401,E402
+from .preprocess import clip_pixel_values, resize, stage2_inputs, stage3_inputs  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -622,6 +622,133 @@ inline MetImg met_img(const void* p, int n, int Hi, int Wi, const int32_t* w) {
     return MetImg{p, n == 1 ? (int64_t)0 : (int64_t)Hi * Wi * 3, Wi, w[0], w[1]};
 }
 
+// ---- input preparation of the evaluation drivers (stage2_batchtest_inpaint_model.py:135-149: Image.resize(..., BICUBIC), canvas pasting,
+// ToTensor + Normalize, CLIPImageProcessor) ------------------------------------------------------------------------------------------------
+// Pillow's 8-bit resampler restated: per axis a table {lo[o], count[o], int32 coeff[o][k]} of 22-bit fixed-point weights (built on the host as
+// Pillow builds them, include/pcdm.h), per output byte clip8((2^21 + sum coeff * pixel) >> 22) in 32-bit integers, the horizontal pass rounded to
+// uint8 before the vertical pass reads it.  The kernels know nothing about the filter.  A table comes from the caller's device memory, so every
+// entry is clamped into the image before it is used: a wrong table gives wrong pixels, never an access outside src, the LDS tile or the window.
+constexpr int kRsTW = 32, kRsTH = 16;           // output tile of resample_tile_kernel
+constexpr int kRsLdsBytes = 24 * 1024;          // most LDS one tile may ask for: 256 rows of 3 channels (6 workgroups a CU); beyond it: two launches
+constexpr int kRsBits = 22;                     // Pillow's PRECISION_BITS for 8-bit images
+
+struct RsAxis {            // tab == nullptr: the axis keeps its size and is copied (Pillow skips that pass)
+    const int32_t* tab;    // [lo (n_out) | count (n_out) | coeff (n_out * k)]
+    int n_out, k, n_in;
+};
+__device__ __forceinline__ void rs_entry(const RsAxis& a, int o, int& lo, int& cnt) {
+    if (!a.tab) { lo = o; cnt = 1; return; }
+    lo = imin(imax(a.tab[o], 0), a.n_in - 1);
+    cnt = imin(imax(a.tab[a.n_out + o], 0), imin(a.k, a.n_in - lo));
+}
+__device__ __forceinline__ const int32_t* rs_coeff(const RsAxis& a, int o) { return a.tab + 2 * (int64_t)a.n_out + (int64_t)o * a.k; }
+__device__ __forceinline__ int rs_clip8(int acc) { return imin(imax(acc >> kRsBits, 0), 255); }
+__host__ __device__ inline int rs_lds_pitch(int C) { return (kRsTW * C + 3) & ~3; }
+
+// One workgroup per 32 x 16 output tile: the input rows [r0, r0 + nrows) its 16 output rows read are resampled horizontally into LDS as uint8
+// (nrows x 32 C bytes: 4.1 KB for 1101 -> 512 rows, never above kRsLdsBytes: the launcher takes the two-launch form instead), then the vertical
+// pass runs out of LDS four bytes per lane and writes dwords where the destination address allows.  dst is the window's first byte.
+__global__ __launch_bounds__(256) void resample_tile_kernel(const uint8_t* __restrict__ src, int C, RsAxis ax, RsAxis ay, uint8_t* __restrict__ dst,
+                                                            int64_t dst_pitch, int max_rows) {
+    PCDM_DYN_SMEM(smem);
+    uint8_t* tile = (uint8_t*)smem;
+    const int tid = threadIdx.x, pitch = rs_lds_pitch(C);
+    const int tx0 = blockIdx.x * kRsTW, ty0 = blockIdx.y * kRsTH;
+    const int tw = imin(kRsTW, ax.n_out - tx0), th = imin(kRsTH, ay.n_out - ty0), rowb = tw * C;
+    int r0, c0, rl, cl;
+    rs_entry(ay, ty0, r0, c0);
+    rs_entry(ay, ty0 + th - 1, rl, cl);
+    const int nrows = imin(imax(r0 + c0, rl + cl) - r0, max_rows);
+    for (int i = tid; i < nrows * rowb; i += 256) {               // horizontal pass: (row, column, channel), the byte index fastest
+        const int row = i / rowb, e = i - row * rowb;
+        const int col = e / C, c = e - col * C;
+        int lo, cnt;
+        rs_entry(ax, tx0 + col, lo, cnt);
+        const uint8_t* p = src + ((int64_t)(r0 + row) * ax.n_in + lo) * C + c;
+        int v = p[0];
+        if (ax.tab) {
+            const int32_t* w = rs_coeff(ax, tx0 + col);
+            int acc = 1 << (kRsBits - 1);
+            for (int k = 0; k < cnt; ++k) acc += w[k] * (int)p[k * C];
+            v = rs_clip8(acc);
+        }
+        tile[row * pitch + e] = (uint8_t)v;
+    }
+    __syncthreads();
+    const int groups = pitch / 4;
+    for (int g = tid; g < th * groups; g += 256) {                // vertical pass: four bytes of one output row per lane
+        const int row = g / groups, e0 = (g - row * groups) * 4;
+        if (e0 >= rowb) continue;
+        int lo, cnt;
+        rs_entry(ay, ty0 + row, lo, cnt);
+        uint32_t out;
+        if (!ay.tab) {
+            out = *(const uint32_t*)(tile + (lo - r0) * pitch + e0);
+        } else {
+            const int32_t* w = rs_coeff(ay, ty0 + row);
+            int a0 = 1 << (kRsBits - 1), a1 = a0, a2 = a0, a3 = a0;
+            for (int k = 0; k < cnt; ++k) {
+                const int rr = lo + k - r0;
+                if (rr < 0 || rr >= nrows) continue;              // (only a table that is not Pillow's)
+                const uint32_t px = *(const uint32_t*)(tile + rr * pitch + e0);
+                const int wk = w[k];
+                a0 += wk * (int)(px & 255u);
+                a1 += wk * (int)((px >> 8) & 255u);
+                a2 += wk * (int)((px >> 16) & 255u);
+                a3 += wk * (int)(px >> 24);
+            }
+            out = (uint32_t)rs_clip8(a0) | ((uint32_t)rs_clip8(a1) << 8) | ((uint32_t)rs_clip8(a2) << 16) | ((uint32_t)rs_clip8(a3) << 24);
+        }
+        uint8_t* d = dst + (int64_t)(ty0 + row) * dst_pitch + (int64_t)tx0 * C + e0;
+        if (e0 + 4 <= rowb && ((uintptr_t)d & 3) == 0) {
+            *(uint32_t*)d = out;
+        } else {
+            for (int j = 0; j < 4 && e0 + j < rowb; ++j) d[j] = (uint8_t)(out >> (8 * j));
+        }
+    }
+}
+
+// One pass of the two-launch form, one output byte per lane straight from global memory: vertical = 0: src [rows, a.n_in, C] -> dst rows of
+// a.n_out pixels; vertical = 1: src [a.n_in, row_px, C] -> a.n_out rows of row_px pixels.
+__global__ __launch_bounds__(256) void resample_axis_kernel(const uint8_t* __restrict__ src, int C, RsAxis a, int vertical, int rows, int row_px,
+                                                            uint8_t* __restrict__ dst, int64_t dst_pitch) {
+    const int rowb = row_px * C;                                  // bytes of an OUTPUT row
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)rows * rowb) return;
+    const int y = (int)(i / rowb), e = (int)(i - (int64_t)y * rowb);
+    const int o = vertical ? y : e / C;
+    int lo, cnt;
+    rs_entry(a, o, lo, cnt);
+    const int64_t step = vertical ? rowb : C;
+    const uint8_t* p = vertical ? src + (int64_t)lo * rowb + e : src + ((int64_t)y * a.n_in + lo) * C + (e - o * C);
+    const int32_t* w = rs_coeff(a, o);
+    int acc = 1 << (kRsBits - 1);
+    for (int k = 0; k < cnt; ++k) acc += w[k] * (int)p[k * step];
+    dst[(int64_t)y * dst_pitch + e] = (uint8_t)rs_clip8(acc);
+}
+
+// out fp32 NCHW [1, C, H, W] <- (x - mean[c]) / std[c] of a window of a uint8 HWC image, x = float(p) / float(scale) (mode 0: ToTensor) or
+// float(double(p) * scale) (mode 1: the numpy rescale of transformers' image processors); one output element per lane, stores coalesced
+struct U8Norm { float mean[4], sd[4]; };
+__global__ __launch_bounds__(256) void u8_to_nchw_kernel(const uint8_t* __restrict__ src, int Ws, int C, int x0, int y0, int W, int H, int mode,
+                                                         double scale, U8Norm nm, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over (c, y, x)
+    if (i >= C * H * W) return;
+    const int c = i / (H * W), r = i - c * H * W;
+    const int y = r / W, x = r - y * W;
+    const uint8_t p = src[((int64_t)(y0 + y) * Ws + x0 + x) * C + c];
+    const float v = mode ? (float)((double)p * scale) : (float)p / (float)scale;
+    out[i] = (v - nm.mean[c]) / nm.sd[c];
+}
+
+inline bool rs_axis_ok(const int32_t* tab, int k, int n_in, int n_out) { return tab ? k > 0 && k <= 1 << 20 : n_in == n_out; }
+// rows of LDS the largest tile can need: lo moves by at most floor(15 n_in / n_out) + 1 over a tile's 16 outputs, the last one reads k rows
+inline int64_t rs_tile_rows(int ky, int Hs, int Hd) {
+    if (Hs == Hd) return kRsTH;
+    const int64_t span = (int64_t)((double)(kRsTH - 1) * (double)Hs / (double)Hd) + 2 + ky;
+    return span < Hs ? span : Hs;
+}
+
 __global__ void advance_step_kernel(int32_t* step) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1;
 }
@@ -908,6 +1035,55 @@ extern "C" int pcdm_select_image(const void* cand_u8, int N, int Hc, int Wc, con
     if (!cand_u8 || N <= 0 || channels != 3 || !met_window_ok(Hc, Wc, win) || !index_dev || !out || (int64_t)win[2] * win[3] * 3 >= (int64_t)1 << 31) return -1;
     PCDM_LAUNCH(select_image_kernel, grid1d((int64_t)win[2] * win[3] * 3, 256), dim3(256), 0, (hipStream_t)s, (const uint8_t*)cand_u8, N, Hc, Wc,
                 win[0], win[1], win[2], win[3], index_dev, out, normalized);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t pcdm_resample_ws_bytes(int Hs, int Ws, int Hd, int Wd, int channels, int ky) {
+    if (Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || (channels != 1 && channels != 3) || (Hs != Hd && ky <= 0)) return -1;
+    if (rs_tile_rows(ky, Hs, Hd) * rs_lds_pitch(channels) <= kRsLdsBytes) return 0;   // one launch
+    return Ws == Wd ? 0 : (int64_t)Hs * Wd * channels;      // the horizontally resampled image between the two launches
+}
+
+extern "C" int pcdm_resample_u8(const void* src, int Hs, int Ws, int channels, const int32_t* xtab, int kx, const int32_t* ytab, int ky, void* dst,
+                                int Hd, int Wd, int64_t dst_pitch, int x0, int y0, void* ws, int64_t ws_bytes, pcdm_stream_t s) {
+    if (!src || !dst || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || (channels != 1 && channels != 3) || x0 < 0 || y0 < 0) return -1;
+    if ((xtab == nullptr) != (Ws == Wd) || (ytab == nullptr) != (Hs == Hd) || !rs_axis_ok(xtab, kx, Ws, Wd) || !rs_axis_ok(ytab, ky, Hs, Hd)) return -1;
+    if (dst_pitch < ((int64_t)x0 + Wd) * channels || (int64_t)Hs * Ws * channels >= (int64_t)1 << 31 || (int64_t)Hd * Wd * channels >= (int64_t)1 << 31) return -1;
+    const int C = channels;
+    const RsAxis ax{xtab, Wd, kx, Ws}, ay{ytab, Hd, ky, Hs};
+    uint8_t* win = (uint8_t*)dst + (int64_t)y0 * dst_pitch + (int64_t)x0 * C;
+    const int64_t rows = rs_tile_rows(ky, Hs, Hd);
+    if (rows * rs_lds_pitch(C) <= kRsLdsBytes) {
+        PCDM_LAUNCH(resample_tile_kernel, dim3((Wd + kRsTW - 1) / kRsTW, (Hd + kRsTH - 1) / kRsTH), dim3(256), (int)rows * rs_lds_pitch(C), (hipStream_t)s,
+                    (const uint8_t*)src, C, ax, ay, win, dst_pitch, (int)rows);
+        PCDM_CHECK_LAUNCH();
+        return 0;
+    }
+    const uint8_t* mid = (const uint8_t*)src;               // rows too far apart for a tile: horizontal pass to the workspace, then the vertical pass
+    if (xtab) {
+        if (!ws || ws_bytes < (int64_t)Hs * Wd * C) return -1;
+        PCDM_LAUNCH(resample_axis_kernel, grid1d((int64_t)Hs * Wd * C, 256), dim3(256), 0, (hipStream_t)s, (const uint8_t*)src, C, ax, 0, Hs, Wd, (uint8_t*)ws,
+                    (int64_t)Wd * C);
+        PCDM_CHECK_LAUNCH();
+        mid = (const uint8_t*)ws;
+    }
+    PCDM_LAUNCH(resample_axis_kernel, grid1d((int64_t)Hd * Wd * C, 256), dim3(256), 0, (hipStream_t)s, mid, C, ay, 1, Hd, Wd, win, dst_pitch);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_u8_to_nchw(const void* src_u8, int Hs, int Ws, int channels, const int32_t* win, int mode, double scale, const float* mean,
+                               const float* std_, float* out, pcdm_stream_t s) {
+    if (!src_u8 || !out || (channels != 1 && channels != 3) || !met_window_ok(Hs, Ws, win) || !mean || !std_ || (mode != 0 && mode != 1)) return -1;
+    if (!(scale > 0.0) || (int64_t)win[2] * win[3] * channels >= (int64_t)1 << 31 || (int64_t)Hs * Ws * channels >= (int64_t)1 << 31) return -1;
+    U8Norm nm{};
+    for (int c = 0; c < channels; ++c) {
+        nm.mean[c] = mean[c];
+        nm.sd[c] = std_[c];
+    }
+    PCDM_LAUNCH(u8_to_nchw_kernel, grid1d((int64_t)win[2] * win[3] * channels, 256), dim3(256), 0, (hipStream_t)s, (const uint8_t*)src_u8, Ws, channels,
+                win[0], win[1], win[2], win[3], mode, scale, nm, out);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

@@ -1014,3 +1014,39 @@ def select_image(cand: torch.Tensor, win: Sequence[int], index: torch.Tensor, ou
     _chk(_lib.lib().pcdm_select_image(_ptr(cand), cand.shape[0], cand.shape[1], cand.shape[2], _win(win), cand.shape[3], _ptr(index), _ptr(out),
                                       int(normalized), _stream(cand)), "pcdm_select_image")
     return out
+
+
+# ------------------------------------------------------------------------------------ input preparation (pcdms_amd/preprocess.py is the public surface)
+def resample_ws_bytes(Hs: int, Ws: int, Hd: int, Wd: int, channels: int, ky: int) -> int:
+    """Workspace bytes of ``resample_u8`` (0: one launch, no workspace); -1: the library refuses the problem."""
+    return int(_lib.lib().pcdm_resample_ws_bytes(Hs, Ws, Hd, Wd, channels, ky))
+
+
+def resample_u8(src: torch.Tensor, xtab: Optional[torch.Tensor], kx: int, ytab: Optional[torch.Tensor], ky: int, dst: torch.Tensor, size: Sequence[int],
+                at: Sequence[int], ws: Optional[torch.Tensor]) -> torch.Tensor:
+    """src uint8 [Hs, Ws, C] -> the window ``size`` = (Wd, Hd) at pixel ``at`` = (x0, y0) of the uint8 canvas dst [Hc, Wc, C], by the int32 device
+    tables of the two axes (None: the axis keeps its size); include/pcdm.h: pcdm_resample_u8."""
+    _c(src, torch.uint8); _c(dst, torch.uint8)
+    assert src.dim() == 3 and dst.dim() == 3 and src.shape[2] == dst.shape[2] and src.device == dst.device, (src.shape, dst.shape)
+    Wd, Hd = int(size[0]), int(size[1])
+    x0, y0 = int(at[0]), int(at[1])
+    if x0 < 0 or y0 < 0 or x0 + Wd > dst.shape[1] or y0 + Hd > dst.shape[0]:
+        raise ValueError(f"a {Wd} x {Hd} window at ({x0}, {y0}) leaves the {dst.shape[1]} x {dst.shape[0]} canvas")
+    for t in (xtab, ytab):
+        if t is not None:
+            _c(t, torch.int32)
+    _chk(_lib.lib().pcdm_resample_u8(_ptr(src), src.shape[0], src.shape[1], src.shape[2], _ptr(xtab), int(kx), _ptr(ytab), int(ky), _ptr(dst), Hd, Wd,
+                                     dst.shape[1] * dst.shape[2], x0, y0, _ptr(ws), 0 if ws is None else ws.numel(), _stream(src)), "pcdm_resample_u8")
+    return dst
+
+
+def u8_to_nchw(src: torch.Tensor, win: Sequence[int], out: torch.Tensor, *, mode: int, scale: float, mean: Sequence[float],
+               std: Sequence[float]) -> torch.Tensor:
+    """out fp32 [1, C, H, W] <- (x - mean[c]) / std[c] over the window (x0, y0, W, H) of src uint8 [Hs, Ws, C]; mode 0: x = float(p) / float(scale),
+    mode 1: x = float(double(p) * scale) (include/pcdm.h: pcdm_u8_to_nchw)."""
+    _c(src, torch.uint8); _c(out, torch.float32)
+    Cn = src.shape[2]
+    assert src.dim() == 3 and out.numel() == Cn * int(win[2]) * int(win[3]) and len(mean) == Cn and len(std) == Cn
+    _chk(_lib.lib().pcdm_u8_to_nchw(_ptr(src), src.shape[0], src.shape[1], Cn, _win(win), int(mode), float(scale), (C.c_float * Cn)(*mean),
+                                    (C.c_float * Cn)(*std), _ptr(out), _stream(src)), "pcdm_u8_to_nchw")
+    return out

@@ -59,8 +59,13 @@ def main(args, rank, select_test_datas):
         s_pose = read_coordinates_file(args.pose_path + d["source_image"].replace(".jpg", ".txt")).to(device).unsqueeze(1)
         t_pose = read_coordinates_file(args.pose_path + d["target_image"].replace(".jpg", ".txt")).to(device).unsqueeze(1)
         load = lambda p: Image.open(p).convert("RGB").resize((args.img_width, args.img_height), Image.BICUBIC)  # noqa: E731
-        clip_s = clip_image_processor(images=load(s_img_path), return_tensors="pt").pixel_values
-        clip_t = clip_image_processor(images=load(t_img_path), return_tensors="pt").pixel_values
+        if getattr(args, "preprocess_device", "host") == "gpu":   # raw pixels up once, resize + CLIP pixels on the device (pcdms_amd/preprocess.py)
+            raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
+            clip_s = P.clip_pixel_values(P.resize(raw(s_img_path), (args.img_width, args.img_height)))
+            clip_t = P.clip_pixel_values(P.resize(raw(t_img_path), (args.img_width, args.img_height)))
+        else:
+            clip_s = clip_image_processor(images=load(s_img_path), return_tensors="pt").pixel_values
+            clip_t = clip_image_processor(images=load(t_img_path), return_tensors="pt").pixel_values
         s_img_embed = image_encoder(clip_s.to(device)).image_embeds.unsqueeze(1)
         target_embed = image_encoder(clip_t.to(device)).image_embeds
         output = pipe(s_embed=s_img_embed, s_pose=s_pose, t_pose=t_pose, num_images_per_prompt=1, num_inference_steps=args.num_inference_steps,
@@ -89,6 +94,9 @@ def build_parser():
     p.add_argument("--num_inference_steps", type=int, default=20)
     p.add_argument("--img_width", type=int, default=512)
     p.add_argument("--img_height", type=int, default=512)
+    p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
+                   help="where the images are resized and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the reference) or gpu "
+                        "(pcdms_amd.preprocess, the same bytes)")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage1_checkpoints/512")
     return p
 

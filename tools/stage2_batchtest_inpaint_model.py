@@ -7,6 +7,8 @@ over ``split_list_into_chunks`` :266-285); every model object is the pcdms_amd o
 embedding, VAE, UNet, scheduler -- runs on the MI355X through libpcdm.so.  What stays host-side is what the reference does
 on the host too: PIL resize / canvas pasting, ``CLIPImageProcessor``, PNG writing, SSIM -- unless ``--metrics_device gpu`` is given: then the samples
 stay on the device as uint8, ``pcdms_amd.metrics.pick_best`` scores and selects there, and only the chosen image and the scores come back.
+With ``--preprocess_device gpu`` the input side moves as well: the decoded pixels of each image are uploaded once as uint8 and
+``pcdms_amd.preprocess`` resizes, pastes, normalises and forms the CLIP pixels on the device -- the same bytes, so the same PNGs and best indices.
 
 Differences, on purpose: ``--img_width`` is honoured (the reference parses it but reads ``args.img_weigh``); ``ImageProjModel_p``
 takes its sizes from the checkpoint / encoder config instead of the literals 1536 / 768 / 1024 (identical for the published
@@ -61,9 +63,9 @@ BEST_INDEX_LOG: list = []   # (output name, index of the saved sample) of every 
 
 def pick_best_on_device(images: torch.Tensor, t_img: Image.Image, window=None):
     """``--metrics_device gpu``: the uint8 NHWC samples stay on the device, the target is uploaded once, pcdms_amd.metrics.pick_best scores the
-    window of every sample and selects the best; only the chosen image, its index and the N scores come back.  Returns
-    (PIL image, index, [scores])."""
-    target = torch.from_numpy(np.array(t_img)).to(images.device)
+    window of every sample and selects the best; only the chosen image, its index and the N scores come back.  ``t_img`` is a PIL image or a uint8
+    [H, W, 3] tensor on the samples' device.  Returns (PIL image, index, [scores])."""
+    target = t_img if isinstance(t_img, torch.Tensor) else torch.from_numpy(np.array(t_img)).to(images.device)   # (already there: --preprocess_device gpu)
     image, index, scores = P.pick_best(images, target, cand_window=window)
     return Image.fromarray(image.cpu().numpy()), int(index.item()), [float(v) for v in scores.tolist()]
 
@@ -124,6 +126,7 @@ def inference(args, rank, select_test_datas):
     print("====================== json_data: {}, model load finish ===================".format(args.json_path.split("/")[-1]))
 
     W, H = args.img_width, args.img_height
+    pre_gpu = getattr(args, "preprocess_device", "host") == "gpu"
     all_ssim = []
     start_time = time.time()
     split = args.json_path.split("/")[-1].split("_")[0]
@@ -132,20 +135,27 @@ def inference(args, rank, select_test_datas):
         t_img_path = args.img_path + data["target_image"].replace(".jpg", ".png")
         s_pose_path = args.pose_path + data["source_image"].replace(".jpg", "_pose.jpg")
         t_pose_path = args.pose_path + data["target_image"].replace(".jpg", "_pose.jpg")
+        t_img_dev = None
         load = lambda p: Image.open(p).convert("RGB").resize((W, H), Image.BICUBIC)  # noqa: E731
-        s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load(s_pose_path), load(t_pose_path)
-        s_img_t_mask = Image.new("RGB", (2 * W, H))          # [source | black]
-        s_img_t_mask.paste(s_img, (0, 0))
-        st_pose = Image.new("RGB", (2 * W, H))               # [source pose | target pose]
-        st_pose.paste(s_pose, (0, 0))
-        st_pose.paste(t_pose, (W, 0))
-
-        pix = clip_image_processor(images=s_img, return_tensors="pt").pixel_values
+        if pre_gpu:      # decode on the host, upload the raw pixels once per image, everything else on the device (pcdms_amd/preprocess.py)
+            raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
+            vae_image, st_pose_t, s_img_u8 = P.stage2_inputs(raw(s_img_path), raw(s_pose_path), raw(t_pose_path), W, H)
+            t_img_dev = P.resize(raw(t_img_path), (W, H))    # also what --metrics_device gpu scores against
+            pix = P.clip_pixel_values(s_img_u8)
+        else:
+            s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load(s_pose_path), load(t_pose_path)
+            s_img_t_mask = Image.new("RGB", (2 * W, H))          # [source | black]
+            s_img_t_mask.paste(s_img, (0, 0))
+            st_pose = Image.new("RGB", (2 * W, H))               # [source pose | target pose]
+            st_pose.paste(s_pose, (0, 0))
+            st_pose.paste(t_pose, (W, 0))
+            pix = clip_image_processor(images=s_img, return_tensors="pt").pixel_values
+            vae_image = to_tensor_normalized(s_img_t_mask).unsqueeze(0)
+            st_pose_t = to_tensor_normalized(st_pose).unsqueeze(0)
         s_img_proj_f = image_proj_model_p(image_encoder_p(pix.to(device)).last_hidden_state)
-        vae_image = to_tensor_normalized(s_img_t_mask).unsqueeze(0)
-        st_pose_f = pose_proj(to_tensor_normalized(st_pose).unsqueeze(0).to(device))
+        st_pose_f = pose_proj(st_pose_t.to(device))
         if split == "train":
-            pix_t = clip_image_processor(images=t_img, return_tensors="pt").pixel_values
+            pix_t = P.clip_pixel_values(t_img_dev) if pre_gpu else clip_image_processor(images=t_img, return_tensors="pt").pixel_values
             pred_t_img_embed = image_encoder_g(pix_t.to(device)).image_embeds.unsqueeze(1)
         elif split == "test":
             name = s_img_path.split("/")[-1].replace(".png", "_to_") + t_img_path.split("/")[-1].replace(".png", ".npy")
@@ -154,12 +164,16 @@ def inference(args, rank, select_test_datas):
             raise ValueError("Check the input JSON file path")
 
         on_device = args.calculate_metrics and getattr(args, "metrics_device", "host") == "gpu"
+        if pre_gpu and not on_device:      # the host scorer and the grid take PIL images: the device's bytes, brought back
+            t_img = Image.fromarray(t_img_dev.cpu().numpy())
+            if not args.calculate_metrics:   # (the grid's thumbnails; the pose halves are not kept as uint8 on the device)
+                s_img, s_pose, t_pose = Image.fromarray(s_img_u8.cpu().numpy()), load(s_pose_path), load(t_pose_path)
         output = pipe(height=H, width=2 * W, guidance_rescale=0.0, vae_image=vae_image, s_img_proj_f=s_img_proj_f, st_pose_f=st_pose_f,
                       pred_t_img_embed=pred_t_img_embed, num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
                       num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
         out_name = s_img_path.split("/")[-1].replace(".png", "") + "_to_" + t_img_path.split("/")[-1]
         if on_device:      # the target half of each [source | generated] canvas against the target, scored where the decoder left it
-            best_img, best, ssim_values = pick_best_on_device(output.images, t_img, (W, 0, W, H))
+            best_img, best, ssim_values = pick_best_on_device(output.images, t_img_dev if pre_gpu else t_img, (W, 0, W, H))
             all_ssim.append(ssim_values[best])
             BEST_INDEX_LOG.append((out_name, best))
             best_img.save(save_dir_metric + out_name)
@@ -214,6 +228,9 @@ def build_parser():
     p.add_argument("--calculate_metrics", action="store_true")
     p.add_argument("--metrics_device", choices=("host", "gpu"), default="host",
                    help="where --calculate_metrics scores the samples: host (scipy, as the reference) or gpu (pcdms_amd.metrics.pick_best)")
+    p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
+                   help="where the inputs are resized, pasted, normalised and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the "
+                        "reference) or gpu (pcdms_amd.preprocess, the same bytes)")
     p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p

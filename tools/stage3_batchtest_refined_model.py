@@ -62,6 +62,7 @@ def inference(args, rank, select_test_datas):
     pipe.enable_xformers_memory_efficient_attention()
     print("====================== json_data: {}, model load finish ===================".format(args.json_path.split("/")[-1]))
     W, H = args.img_width, args.img_height
+    pre_gpu = getattr(args, "preprocess_device", "host") == "gpu"
     all_ssim = []
     start_time = time.time()
     for data in select_test_datas:
@@ -69,17 +70,25 @@ def inference(args, rank, select_test_datas):
         t_img_path = args.img_path + data["target_image"].replace(".jpg", ".png")
         gen_t_img_path = args.gen_t_img_path + s_img_path.split("/")[-1].replace(".png", "_to_") + t_img_path.split("/")[-1]
         load = lambda p: Image.open(p).convert("RGB").resize((W, H), Image.BICUBIC)  # noqa: E731
-        s_img, t_img, gen_t_img = load(s_img_path), load(t_img_path), load(gen_t_img_path)
-        pix = clip_image_processor(images=s_img, return_tensors="pt").pixel_values
-        s_img_proj_f = image_proj_model_p(image_encoder_p(pix.to(device)).last_hidden_state)
-        vae_gen_t_image = to_tensor_normalized(gen_t_img).unsqueeze(0)
         on_device = args.calculate_metrics and getattr(args, "metrics_device", "host") == "gpu"
+        if pre_gpu:      # decode on the host, upload the raw pixels once per image, everything else on the device (pcdms_amd/preprocess.py)
+            raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
+            vae_gen_t_image, s_img_u8 = P.stage3_inputs(raw(s_img_path), raw(gen_t_img_path), W, H)
+            t_img_dev = P.resize(raw(t_img_path), (W, H))    # also what --metrics_device gpu scores against
+            pix = P.clip_pixel_values(s_img_u8)
+            if not on_device:      # the host scorer and the grid take PIL images: the device's bytes, brought back
+                s_img, t_img = Image.fromarray(s_img_u8.cpu().numpy()), Image.fromarray(t_img_dev.cpu().numpy())
+        else:
+            s_img, t_img, gen_t_img = load(s_img_path), load(t_img_path), load(gen_t_img_path)
+            pix = clip_image_processor(images=s_img, return_tensors="pt").pixel_values
+            vae_gen_t_image = to_tensor_normalized(gen_t_img).unsqueeze(0)
+        s_img_proj_f = image_proj_model_p(image_encoder_p(pix.to(device)).last_hidden_state)
         output = pipe(height=H, width=W, guidance_rescale=args.guidance_scale, vae_gen_t_image=vae_gen_t_image, s_img_proj_f=s_img_proj_f,
                       num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
                       num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
         out_name = s_img_path.split("/")[-1].replace(".png", "") + "_to_" + t_img_path.split("/")[-1]
         if on_device:      # the whole refined image against the target, scored on the device (tools/stage2_batchtest_inpaint_model.py)
-            best_img, best, ssim_values = _s2.pick_best_on_device(output.images, t_img)
+            best_img, best, ssim_values = _s2.pick_best_on_device(output.images, t_img_dev if pre_gpu else t_img)
             all_ssim.append(ssim_values[best])
             BEST_INDEX_LOG.append((out_name, best))
             best_img.save(save_dir_metric + out_name)
@@ -126,6 +135,9 @@ def build_parser():
     p.add_argument("--calculate_metrics", action="store_true")
     p.add_argument("--metrics_device", choices=("host", "gpu"), default="host",
                    help="where --calculate_metrics scores the samples: host (scipy, as the reference) or gpu (pcdms_amd.metrics.pick_best)")
+    p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
+                   help="where the inputs are resized, normalised and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the reference) or "
+                        "gpu (pcdms_amd.preprocess, the same bytes)")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage3_checkpoints/512")
     return p
 
