@@ -190,7 +190,17 @@ int pcdm_gemm(const pcdm_gemm_params* p, pcdm_stream_t s);
  *  q  [B*Lq, ldq]  bf16, head h at columns [64h, 64h+64)
  *  k  [B*Lk, ldk]  bf16, same head layout
  *  vt [B, H*64, ldvt] bf16 = V transposed (key index contiguous), as written by PCDM_EPI_SPLIT_VT
- *  o  [B*Lq, ldo]  bf16 */
+ *  o  [B*Lq, ldo]  bf16, columns [0, H*64) of rows [0, B*Lq) written, nothing else
+ *  Any B, H, Lq, Lk >= 1: keys of a partial 64-key tile are masked out of the softmax, tail queries of a partial 128-query block are not
+ *  stored.  The scores may lie anywhere in the fp32 range the softmax can represent: a query whose first key tile scores far below
+ *  the later ones (or whose scores are all far below zero) is computed like any other.  Reruns are bit-identical.
+ *  V^T padding: the columns [Lk, ldvt) of vt that share a 64-key tile with a valid key are READ and multiplied by an exact zero (P of a
+ *  masked key), so they may hold any FINITE value -- the result is bit-identical to zero padding -- but must not hold NaN or Inf
+ *  (0 * NaN = NaN would reach o).  PCDM_EPI_SPLIT_VT does not write them: its consumers allocate the V^T buffer zeroed.
+ *  Returns -1 without launching (o untouched) for: a NULL pointer; B, H, Lq or Lk < 1; ldq, ldk, ldvt or ldo not a multiple of 8
+ *  elements; ldvt < Lk; q, k, vt or o not 16-byte aligned (rows are moved in 16-byte pieces); pcdm_flash_attn_thr: thr_log2 outside
+ *  [0, 16] or NaN.  Returns -2 without launching when Lk * ldk or 64 * ldvt reaches 2^30 elements (the K / V^T tiles are addressed
+ *  with 32-bit byte offsets from the head's first row). */
 int pcdm_flash_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                     void* o, int64_t ldo, int B, int H, int Lq, int Lk, float scale, pcdm_stream_t s);
 /* The same with the lazy-rescale threshold made explicit: the running softmax reference of a query moves only when a key tile's
@@ -205,7 +215,14 @@ int pcdm_flash_attn_thr(const void* q, int64_t ldq, const void* k, int64_t ldk, 
  * pcdm_quantize_fp8: y[r, c] = e4m3(sat(x[r, c] * scale)) for bf16 x [rows, ldx] -> bytes y [rows, ldy]; columns [cols, cols_pad) are
  *   written as zero (cols_pad % 8 == 0).  Used for K [B*Lk, C] and V^T [B*C, Lk -> padded to a multiple of 16].
  * pcdm_flash_attn_fp8: q bf16 as in pcdm_flash_attn; k8 [B*Lk, ldk] / vt8 [B, H*64, ldvt] e4m3 bytes (ldk, ldvt multiples of 16,
- *   ldvt >= Lk, padding zero); k_descale / v_descale undo the quantisation scales; thr_log2 <= 8.  fp32 softmax, P rounded to e4m3. */
+ *   ldvt >= Lk, padding zero); k_descale / v_descale undo the quantisation scales; thr_log2 <= 8.  fp32 softmax, P rounded to e4m3.
+ *   V^T padding: as for pcdm_flash_attn the columns [Lk, ldvt) inside the last key tile are multiplied by an exact zero; pcdm_quantize_fp8
+ *   writes them as zero, and any e4m3 byte other than the NaN patterns 0x7f / 0xff gives the same bits.
+ *   Returns -1 without launching (o untouched) for: a NULL pointer; B, H, Lq or Lk < 1; ldq not a multiple of 8 elements, ldk or ldvt
+ *   not a multiple of 16 bytes, ldo not a multiple of 4 elements (o is stored in 8-byte pieces, so 4 is enough where the bf16 kernel
+ *   needs 8); ldvt < Lk; q, k8 or vt8 not 16-byte aligned, o not 8-byte aligned; thr_log2 outside [0, 8] or NaN (P <= 2^thr must stay
+ *   below e4m3's 448); k_descale or v_descale not > 0 (NaN included).  Returns -2 without launching when Lk * ldk or 64 * ldvt reaches
+ *   2^31 - 1 bytes (32-bit byte offsets). */
 int pcdm_quantize_fp8(const void* x, void* y, int64_t rows, int cols, int cols_pad, int64_t ldx, int64_t ldy, float scale, pcdm_stream_t s);
 int pcdm_flash_attn_fp8(const void* q, int64_t ldq, const void* k8, int64_t ldk, const void* vt8, int64_t ldvt, void* o, int64_t ldo,
                         int B, int H, int Lq, int Lk, float scale, float k_descale, float v_descale, float thr_log2, pcdm_stream_t s);

@@ -192,7 +192,9 @@ __global__ __launch_bounds__(256, 3) void flash_attn_kernel(const u16* __restric
         if (wave_any(bump)) {                                  // wave-uniform: rare after the first tiles
             const float m_new = bump ? bf2f(f2bf(m_ref + mx)) : m_ref;   // bf16-exact
             const float delta = m_new - m_ref;                 // exact: 0 for the queries that stay
-            const float alpha = fast_exp2(-delta);
+            // (the first tile has nothing to rescale: O and the row sum are still zero, and exp2(-delta) is +inf once its maximum lies
+            //  below -128 -- 0 * inf = NaN would poison the query for the rest of the key loop)
+            const float alpha = kb == 0 ? 1.0f : fast_exp2(-delta);
             m_ref = m_new;
             qm[0] = hh == 0 ? f2bf(-m_new) : (u16)0;
 #pragma unroll
@@ -413,7 +415,9 @@ __global__ __launch_bounds__(256, 3) void flash_attn_fp8_kernel(const u16* __res
         if (wave_any(bump)) {
             const float m_new = bump ? bf2f(f2bf(m_ref + mx)) : m_ref;
             const float delta = m_new - m_ref;
-            const float alpha = fast_exp2(-delta);
+            // (the first tile has nothing to rescale: O and the row sum are still zero, and exp2(-delta) is +inf once its maximum lies
+            //  below -128 -- 0 * inf = NaN would poison the query for the rest of the key loop)
+            const float alpha = kb == 0 ? 1.0f : fast_exp2(-delta);
             m_ref = m_new;
             qm[0] = hh == 0 ? f2bf(-m_new) : (u16)0;
 #pragma unroll
@@ -661,6 +665,8 @@ extern "C" int pcdm_flash_attn_fp8(const void* q, int64_t ldq, const void* k8, i
                                    float thr_log2, pcdm_stream_t s) {
     if (!q || !k8 || !vt8 || !o || B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return -1;
     if (ldq % 8 || ldk % 16 || ldvt % 16 || ldo % 4 || ldvt < Lk) return -1;
+    // 16-byte Q row loads and K / V^T LDS-DMA pieces, 8-byte output stores: the base addresses too (as pcdm_flash_attn_thr)
+    if ((((uintptr_t)q | (uintptr_t)k8 | (uintptr_t)vt8) & 15) != 0 || ((uintptr_t)o & 7) != 0) return -1;
     if (!(thr_log2 >= 0.f) || thr_log2 > 8.f || !(k_descale > 0.f) || !(v_descale > 0.f)) return -1;   // P <= 2^thr must stay below 448
     if ((int64_t)Lk * ldk >= 0x7fffffffLL || (int64_t)64 * ldvt >= 0x7fffffffLL) return -2;  // 32-bit buffer offsets
     const dim3 grid((Lq + QPB - 1) / QPB, H, B);
