@@ -10,79 +10,16 @@ pipeline boundary.  ``ImageProjModel_p`` replaces the module defined at :48-64 (
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-from typing import Any, Dict, Optional, Sequence, Tuple
+from typing import Sequence
 
 import torch
 
-from . import _lib, ops
-from ._module import ModuleSurface
+from . import ops
+from ._module import HipModel
 from .ops import BF16
 
 
-class _HipModule(ModuleSurface):
-    """Minimal nn.Module-like surface (to / eval / load_state_dict / state_dict) shared by the two nets."""
-
-    _name = "module"
-
-    def __init__(self):
-        self._device = torch.device("cpu")
-        self._sd: Optional[Dict[str, torch.Tensor]] = None
-        self._w: Optional[Dict[str, Any]] = None
-        self._bufs: Dict[Tuple, torch.Tensor] = {}
-
-    def expected_shapes(self) -> Dict[str, Tuple[int, ...]]:
-        raise NotImplementedError
-
-    @property
-    def device(self):
-        return self._device
-
-    def to(self, *args, **kwargs):
-        device = kwargs.get("device")
-        for a in args:
-            if not isinstance(a, torch.dtype) and a is not None:
-                device = torch.device(a)
-        if device is not None and torch.device(device) != self._device:
-            self._device = torch.device(device)
-            if self._device.type == "cuda" and self._device.index is None:
-                self._device = torch.device("cuda", torch.cuda.current_device())
-            self._w = None
-            self._bufs.clear()
-        return self
-
-    def state_dict(self):
-        return dict(self._sd or {})
-
-    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
-        exp = self.expected_shapes()
-        missing = [k for k in exp if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in exp]
-        bad = [k for k in exp if k in state_dict and tuple(state_dict[k].shape) != tuple(exp[k])]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError(f"Error(s) in loading state_dict for {self._name}: missing {missing[:6]} unexpected "
-                               f"{unexpected[:6]} size mismatch {bad[:6]}")
-        self._sd = {k: state_dict[k].detach().to("cpu", torch.float32) for k in exp if k in state_dict}
-        self._w = None
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
-
-    def _ready(self):
-        if self._sd is None:
-            raise RuntimeError("weights not loaded")
-        if self._device.type != "cuda" and not _lib.is_emulator():
-            raise RuntimeError(f"{self._name} runs on the MI355X only: call .to('cuda')")
-
-    def _buf(self, name, shape, dtype=BF16):
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self._device)
-        return t
-
-
-class ControlNetConditioningEmbedding(_HipModule):
-    _name = "ControlNetConditioningEmbedding"
-
+class ControlNetConditioningEmbedding(HipModel):
     def __init__(self, conditioning_embedding_channels: int = 320, conditioning_channels: int = 3,
                  block_out_channels: Sequence[int] = (16, 32, 96, 256)):
         super().__init__()
@@ -139,9 +76,7 @@ class ControlNetConditioningEmbedding(_HipModule):
     forward = __call__
 
 
-class ImageProjModel_p(_HipModule):
-    _name = "ImageProjModel_p"
-
+class ImageProjModel_p(HipModel):
     def __init__(self, in_dim: int = 1536, hidden_dim: int = 768, out_dim: int = 1024, dropout: float = 0.0):
         super().__init__()
         if in_dim % 64 or hidden_dim % 64 or out_dim % 4:
@@ -179,11 +114,9 @@ class ImageProjModel_p(_HipModule):
     forward = __call__
 
 
-class ImageProjection(_HipModule):
+class ImageProjection(HipModel):
     """``ImageProjection`` of the notebook pipeline (ref src/pipelines/PCDMs_pipeline.py:154-173): Linear(E -> 2E) -> GELU ->
     Linear(2E -> num_tokens * D) -> reshape [-1, num_tokens, D] -> LayerNorm(D).  The same three kernels as ``ImageProjModel_p``."""
-    _name = "ImageProjection"
-
     def __init__(self, cross_attention_dim: int = 768, clip_embeddings_dim: int = 512, num_tokens: int = 4):
         super().__init__()
         if clip_embeddings_dim % 64 or cross_attention_dim % 8:

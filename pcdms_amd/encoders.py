@@ -22,21 +22,31 @@ The position-embedding interpolation (a load-time, weights-only transform) follo
 """
 from __future__ import annotations
 
-import json
 import math
-from pathlib import Path
 from types import SimpleNamespace
 from typing import Any, Dict, Optional, Tuple
 
 import torch
 
 from . import ops
-from .cond import _HipModule
+from ._module import HipModel, read_checkpoint, read_config
 from .ops import BF16
 
 DINOV2_GIANT_CONFIG = dict(hidden_size=1536, num_hidden_layers=40, num_attention_heads=24, mlp_ratio=4, image_size=518,
                            patch_size=14, num_channels=3, layer_norm_eps=1e-6, qkv_bias=True, use_swiglu_ffn=True,
                            layerscale_value=1.0, hidden_act="gelu")
+
+
+def _from_pretrained(cls, path, known, kwargs):
+    """transformers layout: ``config.json`` + ``model.safetensors`` / ``pytorch_model.bin``; keys the model does not have (the text tower of a
+    full CLIPModel checkpoint) are left out."""
+    m = cls(read_config(path, {}, known), **kwargs)
+    sd = read_checkpoint(path, ("model", "pytorch_model"))
+    if sd is None:
+        raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {path}")
+    exp = m.expected_shapes()
+    m.load_state_dict({k: v for k, v in sd.items() if k in exp})
+    return m
 
 
 class BaseModelOutputWithPooling:
@@ -47,9 +57,7 @@ class BaseModelOutputWithPooling:
         return (self.last_hidden_state, self.pooler_output)[i]
 
 
-class Dinov2Model(_HipModule):
-    _name = "Dinov2Model"
-
+class Dinov2Model(HipModel):
     def __init__(self, config: Optional[Any] = None, pos_interp: str = "size", **kwargs):
         super().__init__()
         cfg = dict(DINOV2_GIANT_CONFIG)
@@ -97,31 +105,12 @@ class Dinov2Model(_HipModule):
         exp["layernorm.weight"], exp["layernorm.bias"] = (D,), (D,)
         return exp
 
-    def load_state_dict(self, state_dict, strict: bool = True):
+    def _invalidate(self):
         self._pos_cache.clear()
-        return super().load_state_dict(state_dict, strict)
-
-    def to(self, *args, **kwargs):
-        self._pos_cache.clear()
-        return super().to(*args, **kwargs)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=None, **kwargs):
-        d = Path(str(pretrained_model_name_or_path))
-        cfg = {}
-        if (d / "config.json").exists():
-            cfg = json.loads((d / "config.json").read_text())
-        m = cls(cfg, **kwargs)
-        sd = None
-        if (d / "model.safetensors").exists():
-            from safetensors.torch import load_file
-            sd = load_file(str(d / "model.safetensors"))
-        elif (d / "pytorch_model.bin").exists():
-            sd = torch.load(str(d / "pytorch_model.bin"), map_location="cpu")
-        if sd is None:
-            raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {d}")
-        m.load_state_dict({k: v for k, v in sd.items() if k in m.expected_shapes()})
-        return m
+        return _from_pretrained(cls, pretrained_model_name_or_path, DINOV2_GIANT_CONFIG, kwargs)
 
     # ---------------------------------------------------------------- packing
     def _pack(self):
@@ -179,13 +168,6 @@ class Dinov2Model(_HipModule):
             row0 = self._sd["embeddings.cls_token"][0, 0] + pos[0]
             self._pos_cache[key] = torch.cat([row0[None], patch], 0).to(BF16).to(self._device).contiguous()
         return self._pos_cache[key]
-
-    def _buf(self, name, shape, dtype=BF16, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self._device)
-        return t
 
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
@@ -254,15 +236,13 @@ class CLIPVisionModelOutput:
         return getattr(self, k) if isinstance(k, str) else (self.image_embeds, self.last_hidden_state)[k]
 
 
-class CLIPVisionModelWithProjection(_HipModule):
+class CLIPVisionModelWithProjection(HipModel):
     """``image_encoder_g`` / ``image_encoder`` of the drivers (OpenCLIP ViT-H/14 through transformers):
     ``image_encoder(pixel_values).image_embeds`` -> [B, 1024] (/root/reference/stage1_batchtest_prior_model.py:62,96-98;
     stage2_batchtest_inpaint_model.py:95,178).  Same kernels as ``Dinov2Model``; the head dimension is 80, which the d = 64
     flash kernel does not cover, so attention runs as per-head MFMA GEMMs around one row-softmax launch per layer
     (K Q^T in fp32 -> ``pcdm_softmax_rows`` -> P V), with q / k emitted in a 128-wide zero-padded per-head layout by the
     fused QKV GEMM (the padding lives in the packed weights).  Parity oracle: ``transformers.CLIPVisionModelWithProjection``."""
-
-    _name = "CLIPVisionModelWithProjection"
 
     def __init__(self, config: Optional[Any] = None, **kwargs):
         super().__init__()
@@ -301,26 +281,12 @@ class CLIPVisionModelWithProjection(_HipModule):
         exp["visual_projection.weight"] = (c.projection_dim, D)
         return exp
 
-    def load_state_dict(self, state_dict, strict: bool = True):
-        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}   # buffer in older checkpoints
-        return super().load_state_dict(sd, strict)
+    def _remap_keys(self, sd):
+        return {k: v for k, v in sd.items() if not k.endswith("position_ids")}   # buffer in older checkpoints
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=None, **kwargs):
-        d = Path(str(pretrained_model_name_or_path))
-        cfg = json.loads((d / "config.json").read_text()) if (d / "config.json").exists() else {}
-        m = cls(cfg, **kwargs)
-        sd = None
-        if (d / "model.safetensors").exists():
-            from safetensors.torch import load_file
-            sd = load_file(str(d / "model.safetensors"))
-        elif (d / "pytorch_model.bin").exists():
-            sd = torch.load(str(d / "pytorch_model.bin"), map_location="cpu")
-        if sd is None:
-            raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {d}")
-        exp = m.expected_shapes()
-        m.load_state_dict({k: v for k, v in sd.items() if k in exp})   # a full CLIPModel checkpoint also holds the text tower
-        return m
+        return _from_pretrained(cls, pretrained_model_name_or_path, (*CLIP_VIT_H14_CONFIG, "vision_config"), kwargs)
 
     def _pack(self):
         self._ready()
@@ -364,13 +330,6 @@ class CLIPVisionModelWithProjection(_HipModule):
                                                         torch.cat([bq, bk, sd[a + "v_proj.bias"]], 0), dev),
                                     o=lin(a + "out_proj"), fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
         self._w = w
-
-    def _buf(self, name, shape, dtype=BF16, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self._device)
-        return t
 
     def _attention(self, n, L, B, T):
         """softmax(q k^T / sqrt(dh)) v for every (image, head); returns [B*T, D]."""

@@ -52,6 +52,59 @@ def _c(t: torch.Tensor, dtype) -> torch.Tensor:
     return t
 
 
+# ------------------------------------------------------------------------------------ GEMM tiles, tuner and workspace state
+ROWGEMM_TILES = (31, 32, 33, 34, 35, 36)   # rowgemm.hip (K = 320): id -> (BM, BN) below
+STATS_TILES = (2, 4, 5, 6, 7, 8, 10, 18)   # gemm_ext.hip EXT = 3: the tiles whose STORE epilogue can also write LayerNorm partials (row_stats)
+_STATS_VALID: dict = {}
+LN_TILED = os.environ.get("PCDM_LN_TILED", "1") != "0"
+LN_TILED_TILES = (18, 4, 7, 17, 26, 8, 2)   # gemm.hip dispatch_tile_ln(): the tiled instances that take a folded LayerNorm (any K; row statistics
+#                                             from the A tiles as they pass through LDS) -- levels 1-3 of the UNet, the prior, the encoders
+LN_PARTIALS_TILES = (23,)                     # consumers of producer partials only (mode 2; round 6: the 176-row GEGLU-capable tile)
+# gemm.hip dispatch_tile(): id -> (BM, BN)
+TILE_SHAPES = {1: (256, 128), 2: (64, 64), 3: (256, 64), 4: (128, 128), 5: (128, 64), 6: (256, 64), 7: (128, 128),
+               8: (64, 64), 9: (256, 128), 10: (128, 64), 11: (256, 128), 12: (256, 64), 13: (256, 64), 14: (256, 64),
+               15: (128, 64), 16: (512, 64), 17: (256, 256), 18: (128, 128),
+               21: (192, 320), 26: (192, 256), 22: (176, 320), 23: (176, 256),
+               31: (192, 128), 32: (192, 64), 33: (96, 128), 34: (192, 64), 35: (128, 64), 36: (64, 64)}
+_TUNED: dict = {}
+_WS: dict = {}
+_WS_RETIRED: list = []   # outgrown workspaces are kept: a captured hipGraph may still hold their address
+_WS_GEN: dict = {}
+TUNE_ITERS = 3     # timed launches per candidate (tools/tune_gemm_shapes.py raises it for the committed table)
+TUNE_REPEATS = 1
+TUNE_COLD = False  # tools/tune_gemm_shapes.py --cold: evict L2 / Infinity Cache before every timed launch (inside the denoise step a
+#                    GEMM never finds its 1.74 GB of weights cached; back-to-back launches of one problem do)
+_FLUSH: dict = {}
+
+
+def _launch(t: torch.Tensor, call, name: str, work: float, info: tuple, *extra, key=None) -> int:
+    """``rc = call()`` (one C call that launches one kernel on ``t``'s stream).  While ``LAUNCH_LOG`` is a list and ``t`` is on the device, the
+    call is bracketed by two HIP events on the launch stream and a launch that was accepted (rc 0) is appended as ``(name, algorithmic work, e0,
+    e1, info, *extra)``; ``key``: its tuning-table key, for ``LAUNCH_KEYS``.  A refused call (rc -1: nothing was launched) leaves no entry."""
+    if LAUNCH_LOG is None or not t.is_cuda:
+        return call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = call()
+    if rc == 0:
+        e1.record()
+        LAUNCH_LOG.append((name, work, e0, e1, info, *extra))
+        if LAUNCH_KEYS is not None and key is not None:
+            LAUNCH_KEYS.append((len(LAUNCH_LOG) - 1, key))
+    return rc
+
+
+def _time_launches(fn, iters: int) -> float:
+    """Milliseconds between two HIP events around ``iters`` back-to-back calls of ``fn`` on the current stream (the tuners)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
 # ------------------------------------------------------------------------------------ norms
 def groupnorm_ws(B: int, C: int, device) -> torch.Tensor:
     n = _lib.lib().pcdm_groupnorm_ws_floats(B, C)
@@ -100,10 +153,6 @@ def groupnorm(x1: Union[torch.Tensor, "DeferredGemm"], x2: Optional[torch.Tensor
     C2 = 0 if x2 is None else x2.shape[-1]
     _c(out, BF16); _c(gamma, torch.float32); _c(beta, torch.float32)
     assert ws.numel() >= _lib.lib().pcdm_groupnorm_ws_floats(B, C1 + C2)
-    log = LAUNCH_LOG is not None and out.is_cuda
-    if log:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     if isinstance(x1, DeferredGemm):
         d = x1
         assert d.M == B * HW and d.N == C1 and (d.rowvec is None or d.rpb == HW), "rowvec rows must be the GroupNorm's batch entries"
@@ -113,33 +162,22 @@ def groupnorm(x1: Union[torch.Tensor, "DeferredGemm"], x2: Optional[torch.Tensor
         sp.rowvec_step, sp.rowvec_step_stride = d.rowvec_step, d.rowvec_step_stride
         sp.rowvec_step_count, sp.step_error = d.rowvec_step_count, d.step_error
         sp.pre_out, sp.store_pre = _ptr(_c(d.out, BF16)), int(d.store)
-        rc = _lib.lib().pcdm_groupnorm_splitk(C.byref(sp), _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta), int(silu),
-                                             _ptr(out), _ptr(ws), _stream(out))
-        _chk(rc, "pcdm_groupnorm_splitk")
-        x1 = d.out
+        fn, call = "pcdm_groupnorm_splitk", lambda: _lib.lib().pcdm_groupnorm_splitk(
+            C.byref(sp), _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta), int(silu), _ptr(out), _ptr(ws), _stream(out))
     else:
         _c(x1, BF16)
-        rc = _lib.lib().pcdm_groupnorm(_ptr(x1), C1, _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta),
-                                      int(silu), _ptr(out), _ptr(ws), _stream(x1))
-        _chk(rc, "pcdm_groupnorm")
-    if log:   # algorithmic bytes: the tensor read once + written once
-        e1.record()
-        LAUNCH_LOG.append(("groupnorm", 2.0 * B * HW * (C1 + C2) * 2, e0, e1, (B, HW, C1 + C2)))
+        fn, call = "pcdm_groupnorm", lambda: _lib.lib().pcdm_groupnorm(
+            _ptr(x1), C1, _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta), int(silu), _ptr(out), _ptr(ws), _stream(x1))
+    # algorithmic bytes: the tensor read once + written once
+    _chk(_launch(out, call, "groupnorm", 2.0 * B * HW * (C1 + C2) * 2, (B, HW, C1 + C2)), fn)
     return out
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:
     rows, Cc = x.shape
     _c(x, BF16); _c(out, BF16)
-    log = LAUNCH_LOG is not None and x.is_cuda
-    if log:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _chk(_lib.lib().pcdm_layernorm(_ptr(x), _ptr(out), rows, Cc, eps, _ptr(gamma), _ptr(beta), _stream(x)),
-         "pcdm_layernorm")
-    if log:
-        e1.record()
-        LAUNCH_LOG.append(("layernorm", 2.0 * rows * Cc * 2, e0, e1, (rows, Cc)))
+    _chk(_launch(x, lambda: _lib.lib().pcdm_layernorm(_ptr(x), _ptr(out), rows, Cc, eps, _ptr(gamma), _ptr(beta), _stream(x)),
+                 "layernorm", 2.0 * rows * Cc * 2, (rows, Cc)), "pcdm_layernorm")
     return out
 
 
@@ -427,19 +465,10 @@ def gemm(a: torch.Tensor, pw: PackedWeight, out: torch.Tensor, *, a2: Optional[t
                                     rowvec_step_count=p.rowvec_step_count, step_error=p.step_error,
                                     rpb=p.rows_per_batch, residual=p.residual, ldr=p.ldr, out=out,
                                     store=bool(defer_reduce), keep=(ws, rowvec, residual, pw, rowvec_step, step_error))
-    if LAUNCH_LOG is not None and a.is_cuda:  # bench.py: per-launch HIP events on the launch stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _chk(_lib.lib().pcdm_gemm(C.byref(p), stream), "pcdm_gemm")
-        e1.record()
-        # algorithmic FLOPs stay the un-hoisted 2*M*N*K also when zero_rows skips part of the contraction; the sixth
-        # field is what the launch executes
-        LAUNCH_LOG.append(("gemm_kernel", 2.0 * M * pw.alg_nk, e0, e1, (M, pw.N, pw.K, bool(conv), tile, split),
-                           2.0 * (M - zero_rows) * (pw.exec_nk or pw.alg_nk)))
-        if LAUNCH_KEYS is not None and key is not None:
-            LAUNCH_KEYS.append((len(LAUNCH_LOG) - 1, key))
-        return out if deferred is None else deferred
-    _chk(_lib.lib().pcdm_gemm(C.byref(p), stream), "pcdm_gemm")
+    # algorithmic FLOPs stay the un-hoisted 2*M*N*K also when zero_rows skips part of the contraction; the sixth field is what
+    # the launch executes
+    _chk(_launch(a, lambda: _lib.lib().pcdm_gemm(C.byref(p), stream), "gemm_kernel", 2.0 * M * pw.alg_nk,
+                 (M, pw.N, pw.K, bool(conv), tile, split), 2.0 * (M - zero_rows) * (pw.exec_nk or pw.alg_nk), key=key), "pcdm_gemm")
     return out if deferred is None else deferred
 
 
@@ -465,30 +494,18 @@ def row_stats_reference(a: torch.Tensor) -> torch.Tensor:
     return torch.stack([sm, ((v - sm.unsqueeze(-1) / 32) ** 2).sum(-1)], -1).contiguous()
 
 
-def _gemm_ln(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, out2, vt_col0, tile, row_stats=None, mode=None):
-    """(wrapper: records which entries of LAUNCH_LOG one LayerNorm -> Linear pair produced -- one launch or two, depending on the table -- for
-    tools/tune_in_step.py)"""
-    if LAUNCH_SPANS is None or LAUNCH_LOG is None:
-        return _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, rows_per_batch=rows_per_batch, epilogue=epilogue, out2=out2, vt_col0=vt_col0, tile=tile,
-                             row_stats=row_stats, mode=mode)
-    p0 = len(LAUNCH_LOG)
-    r = _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, rows_per_batch=rows_per_batch, epilogue=epilogue, out2=out2, vt_col0=vt_col0, tile=tile,
-                      row_stats=row_stats, mode=mode)
-    if not tile:
-        LAUNCH_SPANS.append((("ln", a.shape[0], pw.Npad, pw.K, epilogue), p0, len(LAUNCH_LOG)))
-    return r
-
-
-def _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, out2, vt_col0, tile, row_stats=None, mode=None):
+def _gemm_ln(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, out2, vt_col0, tile, row_stats=None):
     """LayerNorm + GEMM: folded into the A-in-registers kernel (K = 320) or an extended instance of the tiled kernel when that wins for the
     shape, two launches otherwise.  Tuned choice per shape = (tile, mode): mode 1 = the kernel takes the row statistics itself, mode 2 = it
-    merges the partials its producer wrote (``row_stats``; falls back to mode 1 on the same tile when the producer could not write them)."""
+    merges the partials its producer wrote (``row_stats``; falls back to mode 1 on the same tile when the producer could not write them).
+    For tools/tune_in_step.py, ``LAUNCH_SPANS`` gets the entries of ``LAUNCH_LOG`` the pair produced -- one launch or two, depending on the table."""
     gamma, beta, eps = ln
     M = a.shape[0]
     assert a.dtype == BF16 and a.stride(1) == 1 and a.shape[1] == pw.K and ln_buf.shape[0] >= M
     key = ("ln", M, pw.Npad, pw.K, epilogue)
+    span0 = len(LAUNCH_LOG) if (LAUNCH_SPANS is not None and LAUNCH_LOG is not None and not tile) else None
     have_stats = row_stats_valid(row_stats)
-    choice = (tile, mode or (2 if have_stats else 1)) if tile else _TUNED.get(key)   # (an explicit tile: partials are used when there are valid ones)
+    choice = (tile, 2 if have_stats else 1) if tile else _TUNED.get(key)   # (an explicit tile: partials are used when there are valid ones)
     if not LN_TILED and not tile and pw.K != 320:   # PCDM_LN_TILED=0: A/B switch -- levels 1-3 keep their LayerNorm launches
         pw_ln = None
     stream = _stream(a)
@@ -514,23 +531,15 @@ def _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, ou
         n = layernorm(a, gamma, beta, eps, ln_buf[:M])
         return gemm(n, pw, out, rows_per_batch=rows_per_batch, epilogue=epilogue, out2=out2, vt_col0=vt_col0)
 
-    if pw_ln is None or pw_ln.wsum is None:
-        assert not tile
-        two_launches()
-        return out
-    if choice is None and AUTOTUNE and a.is_cuda and not torch.cuda.is_current_stream_capturing():
+    foldable = pw_ln is not None and pw_ln.wsum is not None
+    assert foldable or not tile
+    if foldable and choice is None and AUTOTUNE and a.is_cuda and not torch.cuda.is_current_stream_capturing():
         two_launches()                         # (tunes the plain GEMM of this shape on the way)
         ref = out.float().clone()
 
-        def timed(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        def timed(fn):   # one warm launch, then TUNE_ITERS timed ones
             fn()
-            e0.record()
-            for _ in range(TUNE_ITERS):
-                fn()
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1)
+            return _time_launches(fn, TUNE_ITERS)
         best, best_t = (0, 1), timed(two_launches)
         ref_stats = row_stats_reference(a) if (row_stats is not None and pw.K != 320 and pw.K % 64 == 0 and pw.K <= 1280) else None   # (a caller that has a producer)
         for t in (ROWGEMM_TILES if pw.K == 320 else ()) + LN_TILED_TILES + LN_PARTIALS_TILES:
@@ -547,52 +556,24 @@ def _gemm_ln_impl(a, pw, pw_ln, out, ln, ln_buf, *, rows_per_batch, epilogue, ou
     md = 1
     if isinstance(choice, tuple):
         choice, md = choice[0], (choice[1] if len(choice) > 1 else 1)
-    if choice and pw_ln is not None and pw_ln.wsum is not None:
+    if choice and foldable:
         stats = row_stats if (md == 2 and have_stats) else None     # (mode 2 without valid partials: the same tile takes its own statistics)
-        fused_ = lambda t: fused(t, stats)  # noqa: E731
         # The table key does not hold rows_per_batch: (2816, 3840, 1280, q|k|v^T) is level 2 at UNet batch 8 (352 tokens per image: fine) and
         # level 3 at batch 32 (88 tokens: the folded instances need a multiple of 32 for the V^T pass and refuse).  A refusal (-1) comes
         # before anything is launched: take the two-launch form then -- also inside a graph capture.
-        log = LAUNCH_LOG is not None and a.is_cuda
-        if log:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = fused_(choice)
+        rc = _launch(a, lambda: fused(choice, stats), "gemm_kernel", 2.0 * M * pw.alg_nk, (M, pw.N, pw.K, False, choice, 1), 2.0 * M * pw.alg_nk,
+                     key=None if tile else key)
         if rc == -1 and not tile:
             if LN_REFUSED is not None:
                 LN_REFUSED.add(key)
             two_launches()
-            return out
-        _chk(rc, "pcdm_gemm (LayerNorm folded)")
-        if log:
-            e1.record()
-            LAUNCH_LOG.append(("gemm_kernel", 2.0 * M * pw.alg_nk, e0, e1, (M, pw.N, pw.K, False, choice, 1), 2.0 * M * pw.alg_nk))
-            if LAUNCH_KEYS is not None and not tile:
-                LAUNCH_KEYS.append((len(LAUNCH_LOG) - 1, key))
-        return out
-    two_launches()
+        else:
+            _chk(rc, "pcdm_gemm (LayerNorm folded)")
+    else:
+        two_launches()
+    if span0 is not None:
+        LAUNCH_SPANS.append((key, span0, len(LAUNCH_LOG)))
     return out
-
-
-ROWGEMM_TILES = (31, 32, 33, 34, 35, 36)   # rowgemm.hip (K = 320): id -> (BM, BN) below
-STATS_TILES = (2, 4, 5, 6, 7, 8, 10, 18)   # gemm_ext.hip EXT = 3: the tiles whose STORE epilogue can also write LayerNorm partials (row_stats)
-_STATS_VALID: dict = {}
-LN_TILED = os.environ.get("PCDM_LN_TILED", "1") != "0"
-LN_TILED_TILES = (18, 4, 7, 17, 26, 8, 2)   # gemm.hip dispatch_tile_ln(): the tiled instances that take a folded LayerNorm (any K; row statistics
-#                                             from the A tiles as they pass through LDS) -- levels 1-3 of the UNet, the prior, the encoders
-LN_PARTIALS_TILES = (23,)                     # consumers of producer partials only (mode 2; round 6: the 176-row GEGLU-capable tile)
-# gemm.hip dispatch_tile(): id -> (BM, BN)
-TILE_SHAPES = {1: (256, 128), 2: (64, 64), 3: (256, 64), 4: (128, 128), 5: (128, 64), 6: (256, 64), 7: (128, 128),
-               8: (64, 64), 9: (256, 128), 10: (128, 64), 11: (256, 128), 12: (256, 64), 13: (256, 64), 14: (256, 64),
-               15: (128, 64), 16: (512, 64), 17: (256, 256), 18: (128, 128),
-               21: (192, 320), 26: (192, 256), 22: (176, 320), 23: (176, 256),
-               31: (192, 128), 32: (192, 64), 33: (96, 128), 34: (192, 64), 35: (128, 64), 36: (64, 64)}
-_TUNED: dict = {}
-_WS: dict = {}
-
-
-_WS_RETIRED: list = []   # outgrown workspaces are kept: a captured hipGraph may still hold their address
-_WS_GEN: dict = {}
 
 
 def workspace_generation(device) -> int:
@@ -612,13 +593,6 @@ def _splitk_ws(device, floats: int) -> torch.Tensor:
         ws = _WS[device] = torch.empty(max(floats, 1 << 24), dtype=torch.float32, device=device)
         _WS_GEN[device] = _WS_GEN.get(device, 0) + 1
     return ws
-
-
-TUNE_ITERS = 3     # timed launches per candidate (tools/tune_gemm_shapes.py raises it for the committed table)
-TUNE_REPEATS = 1
-TUNE_COLD = False  # tools/tune_gemm_shapes.py --cold: evict L2 / Infinity Cache before every timed launch (inside the denoise step a
-#                    GEMM never finds its 1.74 GB of weights cached; back-to-back launches of one problem do)
-_FLUSH: dict = {}
 
 
 def _flush_caches(device):
@@ -674,13 +648,7 @@ def _autotune(p: GemmParams, stream, pw: PackedWeight, epilogue: int, device, ou
                     evs[-1][1].synchronize()
                     t = min(t, sum(a.elapsed_time(b) for a, b in evs))
                     continue
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(TUNE_ITERS):
-                    fn(C.byref(p), stream)
-                e1.record()
-                e1.synchronize()
-                t = min(t, e0.elapsed_time(e1))
+                t = min(t, _time_launches(lambda: fn(C.byref(p), stream), TUNE_ITERS))
             if t < best_t:
                 best, best_t = (tile, sk), t
     p.split_k, p.ws, p.ws_floats = 0, None, 0
@@ -721,20 +689,12 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
         assert t.dtype == BF16
     assert q.stride(1) == 1 and k.stride(1) == 1 and vt.is_contiguous() and out.stride(1) == 1
     scale = scale if scale is not None else 1.0 / math.sqrt(64)
-    log = LAUNCH_LOG is not None and q.is_cuda
-    if log:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out), out.stride(0), B, H, Lq, Lk, scale)
     if thr is None:
-        rc = _lib.lib().pcdm_flash_attn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out),
-                                       out.stride(0), B, H, Lq, Lk, scale, _stream(q))
+        call = lambda: _lib.lib().pcdm_flash_attn(*args, _stream(q))  # noqa: E731
     else:   # explicit lazy-rescale threshold (log2 units; 0 = eager online softmax)
-        rc = _lib.lib().pcdm_flash_attn_thr(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out),
-                                           out.stride(0), B, H, Lq, Lk, scale, float(thr), _stream(q))
-    _chk(rc, "pcdm_flash_attn")
-    if log:
-        e1.record()
-        LAUNCH_LOG.append(("flash_attn_kernel", 4.0 * B * H * Lq * Lk * 64, e0, e1, (B, H, Lq, Lk)))
+        call = lambda: _lib.lib().pcdm_flash_attn_thr(*args, float(thr), _stream(q))  # noqa: E731
+    _chk(_launch(q, call, "flash_attn_kernel", 4.0 * B * H * Lq * Lk * 64, (B, H, Lq, Lk)), "pcdm_flash_attn")
     return out
 
 
@@ -747,16 +707,9 @@ def attn_wide(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Ten
     assert q.stride(1) == 1 and k.stride(1) == 1 and vt.is_contiguous() and vt.dim() == 3 and out.stride(1) == 1
     d = vt.shape[1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
-    log = LAUNCH_LOG is not None and q.is_cuda
-    if log:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _lib.lib().pcdm_attn_wide(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out), out.stride(0),
-                                   B, Lq, Lk, d, scale, _stream(q))
-    _chk(rc, "pcdm_attn_wide")
-    if log:
-        e1.record()
-        LAUNCH_LOG.append(("attn_wide_kernel", 4.0 * B * Lq * Lk * d, e0, e1, (B, Lq, Lk, d)))
+    _chk(_launch(q, lambda: _lib.lib().pcdm_attn_wide(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(vt), vt.shape[-1], _ptr(out), out.stride(0),
+                                                      B, Lq, Lk, d, scale, _stream(q)),
+                 "attn_wide_kernel", 4.0 * B * Lq * Lk * d, (B, Lq, Lk, d)), "pcdm_attn_wide")
     return out
 
 
@@ -779,16 +732,10 @@ def flash_attn_fp8(q: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, out: to
     assert q.dtype == BF16 and out.dtype == BF16 and k8.dtype == FP8 and vt8.dtype == FP8
     assert q.stride(1) == 1 and k8.stride(1) == 1 and vt8.is_contiguous() and out.stride(1) == 1
     scale = scale if scale is not None else 1.0 / math.sqrt(64)
-    log = LAUNCH_LOG is not None and q.is_cuda
-    if log:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _lib.lib().pcdm_flash_attn_fp8(_ptr(q), q.stride(0), _ptr(k8), k8.stride(0), _ptr(vt8), vt8.shape[-1], _ptr(out), out.stride(0),
-                                       B, H, Lq, Lk, scale, float(k_descale), float(v_descale), float(thr), _stream(q))
-    _chk(rc, "pcdm_flash_attn_fp8")
-    if log:
-        e1.record()
-        LAUNCH_LOG.append(("flash_attn_fp8_kernel", 4.0 * B * H * Lq * Lk * 64, e0, e1, (B, H, Lq, Lk)))
+    _chk(_launch(q, lambda: _lib.lib().pcdm_flash_attn_fp8(_ptr(q), q.stride(0), _ptr(k8), k8.stride(0), _ptr(vt8), vt8.shape[-1], _ptr(out),
+                                                           out.stride(0), B, H, Lq, Lk, scale, float(k_descale), float(v_descale), float(thr),
+                                                           _stream(q)),
+                 "flash_attn_fp8_kernel", 4.0 * B * H * Lq * Lk * 64, (B, H, Lq, Lk)), "pcdm_flash_attn_fp8")
     return out
 
 

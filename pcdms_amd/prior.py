@@ -16,15 +16,13 @@ kernel (32 heads, 6 keys), Linear+GELU / Linear+SiLU by the activation epilogue,
 from __future__ import annotations
 
 import json
-import math
 from pathlib import Path
-from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib, ops
-from .cond import _HipModule
+from . import ops
+from ._module import Config, HipModel, default_init, read_checkpoint, read_config
 from .ops import BF16
 from .schedulers import UnCLIPScheduler
 
@@ -42,17 +40,7 @@ class PriorTransformerOutput:
         return (self.predicted_image_embedding,)[i]
 
 
-class _Config(SimpleNamespace):
-    def __getitem__(self, k):
-        return getattr(self, k)
-
-    def get(self, k, d=None):
-        return getattr(self, k, d)
-
-
-class Stage1_PriorTransformer(_HipModule):
-    _name = "Stage1_PriorTransformer"
-
+class Stage1_PriorTransformer(HipModel):
     def __init__(self, num_attention_heads: int = 32, attention_head_dim: int = 64, num_layers: int = 20,
                  embedding_dim: int = 768, num_embeddings=77, additional_embeddings=4, dropout: float = 0.0, **kwargs):
         super().__init__()
@@ -61,19 +49,14 @@ class Stage1_PriorTransformer(_HipModule):
         if embedding_dim != _POSE_OUT:
             raise NotImplementedError("embedding_dim must be 1024: the reference's pose MLP emits 1024 features "
                                       "(stage1_prior_transformer.py:97-98) into Linear(embedding_dim, inner_dim)")
-        self.config = _Config(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim,
+        self.config = Config(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim,
                               num_layers=num_layers, embedding_dim=embedding_dim, num_embeddings=num_embeddings,
                               additional_embeddings=additional_embeddings, dropout=dropout,
                               **{k: v for k, v in kwargs.items() if k.startswith("_")})
         self.clip_mean, self.clip_std = torch.tensor(CLIP_MEAN), torch.tensor(CLIP_STD)
-        self._dtype = torch.float32
         self._static: Optional[Tuple] = None
 
     # ---------------------------------------------------------------- module-like surface
-    @property
-    def dtype(self):
-        return self._dtype
-
     @property
     def inner_dim(self) -> int:
         return self.config.num_attention_heads * self.config.attention_head_dim
@@ -82,15 +65,8 @@ class Stage1_PriorTransformer(_HipModule):
     def num_tokens(self) -> int:
         return self.config.num_embeddings + self.config.additional_embeddings
 
-    def to(self, *args, **kwargs):
-        for a in list(args) + [kwargs.get("dtype")]:
-            if isinstance(a, torch.dtype):
-                self._dtype = a
+    def _invalidate(self):
         self._static = None
-        return super().to(*args, **kwargs)
-
-    def half(self):
-        return self.to(torch.float16)
 
     def expected_shapes(self) -> Dict[str, Tuple[int, ...]]:
         c, D, E = self.config, self.inner_dim, self.config.embedding_dim
@@ -119,10 +95,6 @@ class Stage1_PriorTransformer(_HipModule):
         ln("norm_out", D); lin("proj_to_clip_embeddings", E, D)
         return exp
 
-    def load_state_dict(self, state_dict, strict: bool = True):
-        self._static = None
-        return super().load_state_dict(state_dict, strict)
-
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder: Optional[str] = None, torch_dtype=None,
                         low_cpu_mem_usage: bool = False, ignore_mismatched_sizes: bool = False, **kwargs):
@@ -132,34 +104,14 @@ class Stage1_PriorTransformer(_HipModule):
         does -- the driver then overwrites everything with ``load_state_dict`` (:58-59)."""
         d = Path(str(pretrained_model_name_or_path))
         d = d / subfolder if subfolder else d
-        cfg = dict(KANDINSKY22_PRIOR_CONFIG)
-        if (d / "config.json").exists():
-            cfg.update({k: v for k, v in json.loads((d / "config.json").read_text()).items() if k in cfg or k.startswith("_")})
-        cfg.update(kwargs)
-        m = cls(**cfg)
+        m = cls(**{**read_config(d, KANDINSKY22_PRIOR_CONFIG), **kwargs})
         exp = m.expected_shapes()
-        g = torch.Generator().manual_seed(0)
-        sd = {}
-        for k, shp in exp.items():   # fresh init
-            wk = k[: k.rfind(".") + 1] + "weight"
-            if k in ("positional_embedding", "prd_embedding"):
-                sd[k] = torch.zeros(shp)
-            elif len(exp[wk]) == 1:
-                sd[k] = torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
-            else:
-                sd[k] = (torch.rand(shp, generator=g) * 2 - 1) / math.sqrt(exp[wk][1])
-        loaded = None
-        if (d / "diffusion_pytorch_model.safetensors").exists():
-            from safetensors.torch import load_file
-            loaded = load_file(str(d / "diffusion_pytorch_model.safetensors"))
-        elif (d / "diffusion_pytorch_model.bin").exists():
-            loaded = torch.load(str(d / "diffusion_pytorch_model.bin"), map_location="cpu")
-        if loaded is not None:
-            for k, v in loaded.items():
-                if k in exp and tuple(v.shape) == tuple(exp[k]):
-                    sd[k] = v
-                elif k in exp and not ignore_mismatched_sizes:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {exp[k]}")
+        sd = default_init(exp, 0, zeros=("positional_embedding", "prd_embedding"), divide=True)
+        for k, v in (read_checkpoint(d, ("diffusion_pytorch_model",)) or {}).items():
+            if k in exp and tuple(v.shape) == tuple(exp[k]):
+                sd[k] = v
+            elif k in exp and not ignore_mismatched_sizes:
+                raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {exp[k]}")
         m.load_state_dict(sd)
         if torch_dtype is not None:
             m.to(torch_dtype)
@@ -288,14 +240,6 @@ class Stage1_PriorTransformer(_HipModule):
         return PriorTransformerOutput(pred) if return_dict else (pred,)
 
     __call__ = forward
-
-    def _buf(self, name, shape, dtype=BF16, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self._device)
-        return t
-
 
 class KandinskyPriorPipelineOutput:
     def __init__(self, image_embeds, negative_image_embeds):

@@ -18,8 +18,6 @@ addresses cannot be recycled while the entry lives) and compares tensor identity
 """
 from __future__ import annotations
 
-import json
-import math
 import os
 from pathlib import Path
 from types import SimpleNamespace
@@ -28,7 +26,7 @@ from typing import Any, Dict, Iterator, List, Optional, Tuple, Union
 import torch
 
 from . import ops
-from ._module import ModuleSurface
+from ._module import Config, HipModel, default_init, read_checkpoint, read_config
 from .ops import BF16, PackedWeight
 
 SHARE_CFG_PREFIX = os.environ.get("PCDM_SHARE_CFG_PREFIX", "1") != "0"   # A/B switch (tools/README.md)
@@ -98,17 +96,6 @@ class UNet2DConditionOutput:
         return (self.sample,)
 
 
-class _Config(SimpleNamespace):
-    def __getitem__(self, k):
-        return getattr(self, k)
-
-    def get(self, k, d=None):
-        return getattr(self, k, d)
-
-    def keys(self):
-        return self.__dict__.keys()
-
-
 def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (list, tuple)) else (v,) * n
 
@@ -130,12 +117,13 @@ class Conditioning:
         self.kv: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
-class Stage2_InapintUNet2DConditionModel(ModuleSurface):
+class Stage2_InapintUNet2DConditionModel(HipModel):
     """Drop-in for the reference class of the same (sic) name; inference only."""
 
     _pose_required = True   # the stage-2 forward adds my_pose_cond unconditionally (ref :742)
 
     def __init__(self, **kwargs):
+        super().__init__()
         cfg = dict(_DEFAULT_CONFIG)
         unknown = [k for k in kwargs if k not in cfg and not k.startswith("_")]
         if unknown:
@@ -153,7 +141,7 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
             raise ValueError("Must provide the same number of down/up block types and block_out_channels")
         cfg.setdefault("_class_name", "Stage2_InapintUNet2DConditionModel")
         cfg.setdefault("_diffusers_version", "0.24.0")
-        self.config = _Config(**cfg)
+        self.config = Config(**cfg)
         heads = cfg["num_attention_heads"] or cfg["attention_head_dim"]  # ref :122-128 (mis-named head COUNT)
         self._heads = _as_tuple(heads, n)
         self._boc = tuple(cfg["block_out_channels"])
@@ -169,36 +157,11 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
             raise NotImplementedError("cross_attention_dim must be an int multiple of 64")
         self.num_upsamplers = n - 1
         self.sample_size = cfg["sample_size"]
-        self._device = torch.device("cpu")
-        self._dtype = torch.float32
-        self._sd: Optional[Dict[str, torch.Tensor]] = None   # fp32 CPU master copy (diffusers key names)
-        self._w: Optional[Dict[str, Any]] = None             # packed device weights
-        self._bufs: Dict[Tuple, torch.Tensor] = {}
         self._cache: Dict[str, Any] = {}
         self._cond_gen = 0   # bumped by every prepare_conditioning (the shared K/V, pose and class-embedding buffers are rewritten)
         self._attn_fp8 = False   # e4m3 K / V^T / Q / P attention on the MX-scaled fp8 MFMA (set_attention_precision)
 
     # ------------------------------------------------------------------ nn.Module-like surface
-    @property
-    def dtype(self):
-        return self._dtype
-
-    @property
-    def device(self):
-        return self._device
-
-    def modules(self):
-        return iter(())
-
-    def parameters(self):
-        return iter((self._sd or {}).values())
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag: bool = False):
-        return self
-
     def set_use_memory_efficient_attention_xformers(self, valid: bool = True, attention_op=None):
         """No-op: the fused HIP attention kernel is always used (ref stage2_batchtest_inpaint_model.py:133)."""
 
@@ -218,68 +181,12 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
             self._cond_gen += 1                                   # outstanding Conditioning objects lack / carry the e4m3 K, V^T
         return self
 
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            elif a is not None:
-                device = torch.device(a)
-        if dtype is not None:
-            self._dtype = dtype  # I/O dtype only; arithmetic is bf16 x bf16 -> fp32 on MFMA
-        if device is not None and torch.device(device) != self._device:
-            self._device = torch.device(device)
-            if self._device.type == "cuda" and self._device.index is None:
-                self._device = torch.device("cuda", torch.cuda.current_device())
-            self._w = None
-            self._bufs.clear()
-            self._cache.clear()
-        return self
-
-    def half(self):
-        return self.to(torch.float16)
+    def _invalidate(self):
+        self._cache.clear()
 
     # ------------------------------------------------------------------ weights
     def expected_shapes(self) -> Dict[str, Tuple[int, ...]]:
         return dict(_param_shapes(self))
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        if self._sd is None:
-            raise RuntimeError("no weights loaded")
-        return dict(self._sd)
-
-    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
-        exp = self.expected_shapes()
-        missing = [k for k in exp if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in exp]
-        bad = [f"{k}: {tuple(state_dict[k].shape)} vs {exp[k]}" for k in exp
-               if k in state_dict and tuple(state_dict[k].shape) != tuple(exp[k])]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError("Error(s) in loading state_dict for Stage2_InapintUNet2DConditionModel:\n"
-                               f"  Missing key(s): {missing[:8]}{'...' if len(missing) > 8 else ''}\n"
-                               f"  Unexpected key(s): {unexpected[:8]}{'...' if len(unexpected) > 8 else ''}\n"
-                               f"  size mismatch: {bad[:8]}")
-        base = self._sd or {}
-        self._sd = {k: (state_dict[k].detach().to("cpu", torch.float32) if k in state_dict else base[k]) for k in exp}
-        self._w = None
-        self._cache.clear()
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
-
-    def init_weights(self, seed: int = 0):
-        """PyTorch-default init (what from_pretrained leaves in re-initialised tensors)."""
-        g = torch.Generator().manual_seed(seed)
-        exp = self.expected_shapes()
-        sd = {}
-        for k, shp in exp.items():
-            wk = k[: k.rfind(".") + 1] + "weight"
-            if len(exp[wk]) == 1:
-                sd[k] = torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
-            else:
-                bound = 1.0 / math.sqrt(math.prod(exp[wk][1:]))
-                sd[k] = (torch.rand(shp, generator=g) * 2 - 1) * bound
-        self._sd = sd
-        self._w = None
-        return self
 
     @classmethod
     def from_config(cls, config, **kwargs):
@@ -297,21 +204,12 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
         A path without config.json falls back to the SD-2.1-base UNet config."""
         root = Path(str(pretrained_model_name_or_path))
         d = root / subfolder if subfolder else root
-        cfg = dict(SD21_BASE_UNET_CONFIG)
-        cj = d / "config.json"
-        if cj.exists():
-            cfg = {k: v for k, v in json.loads(cj.read_text()).items() if k in _DEFAULT_CONFIG or k.startswith("_")}
-        cfg.update(kwargs)
-        model = cls(**cfg)
-        model.init_weights(seed=0)
-        sd = None
-        if (d / "diffusion_pytorch_model.safetensors").exists():
-            from safetensors.torch import load_file
-            sd = load_file(str(d / "diffusion_pytorch_model.safetensors"))
-        elif (d / "diffusion_pytorch_model.bin").exists():
-            sd = torch.load(str(d / "diffusion_pytorch_model.bin"), map_location="cpu")
+        cfg = read_config(d, {}, _DEFAULT_CONFIG) if (d / "config.json").exists() else dict(SD21_BASE_UNET_CONFIG)
+        model = cls(**{**cfg, **kwargs})
+        exp = model.expected_shapes()
+        model.load_state_dict(default_init(exp, 0))
+        sd = read_checkpoint(d, ("diffusion_pytorch_model",))
         if sd is not None:
-            exp = model.expected_shapes()
             mism = [k for k in sd if k in exp and tuple(sd[k].shape) != tuple(exp[k])]
             if mism and not ignore_mismatched_sizes:
                 raise ValueError(f"size mismatch for {mism}; pass ignore_mismatched_sizes=True")
@@ -322,11 +220,7 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
 
     # ------------------------------------------------------------------ packing
     def _pack(self):
-        if self._sd is None:
-            raise RuntimeError("weights not loaded: call load_state_dict / from_pretrained first")
-        if self._device.type != "cuda" and not _emu():
-            raise RuntimeError("Stage2_InapintUNet2DConditionModel runs on the MI355X only: call .to('cuda') "
-                               "(there is no CPU implementation)")
+        self._ready()
         self._pack_gen = getattr(self, "_pack_gen", 0) + 1   # a captured hipGraph holds pointers into the packed weights
         sd, dev = self._sd, self._device
         w: Dict[str, Any] = {}
@@ -407,14 +301,6 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
         self._w = w
 
     # ------------------------------------------------------------------ scratch / caches
-    def _buf(self, name: str, shape, dtype=BF16, zero: bool = False) -> torch.Tensor:
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self._device)
-            self._bufs[key] = t
-        return t
-
     def invalidate_caches(self):
         """Drop the bare-``forward`` conditioning cache (and the references it holds to the caller's tensors)."""
         self._cache.clear()
@@ -816,11 +702,6 @@ class Stage2_InapintUNet2DConditionModel(ModuleSurface):
             for nm_, (t_, _, _) in zip(names, all_skips):
                 taps[nm_] = t_.clone()
         return out
-
-
-def _emu() -> bool:
-    from . import _lib
-    return _lib.is_emulator()
 
 
 # ---------------------------------------------------------------------- topology walkers

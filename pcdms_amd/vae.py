@@ -12,29 +12,17 @@ folded exactly into ``encoder.conv_out`` at pack time.
 """
 from __future__ import annotations
 
-import json
-import math
 from pathlib import Path
-from types import SimpleNamespace
 from typing import Any, Dict, Iterator, Optional, Tuple
 
 import torch
 
-from . import _lib, ops
-from ._module import ModuleSurface
-from .ops import BF16
+from . import _lib, ops, unet
+from ._module import Config, HipModel, read_checkpoint, read_config
 
 SD21_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
                        layers_per_block=2, norm_num_groups=32, scaling_factor=0.18215, sample_size=768, act_fn="silu",
                        down_block_types=("DownEncoderBlock2D",) * 4, up_block_types=("UpDecoderBlock2D",) * 4)
-
-
-class _Config(SimpleNamespace):
-    def __getitem__(self, k):
-        return getattr(self, k)
-
-    def get(self, k, d=None):
-        return getattr(self, k, d)
 
 
 class DiagonalGaussianDistribution:
@@ -72,89 +60,35 @@ class DecoderOutput:
         return (self.sample,)[i]
 
 
-class AutoencoderKL(ModuleSurface):
+class AutoencoderKL(HipModel):
+    _reshape_same_numel = True
+
     def __init__(self, **kwargs):
+        super().__init__()
         cfg = dict(SD21_VAE_CONFIG)
         cfg.update({k: v for k, v in kwargs.items() if k in cfg or k.startswith("_")})
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
-        self.config = _Config(**cfg)
+        self.config = Config(**cfg)
         for c in cfg["block_out_channels"]:
             if c % 64:
                 raise NotImplementedError("block_out_channels must be multiples of 64")
-        self._device = torch.device("cpu")
-        self._dtype = torch.float32
-        self._sd: Optional[Dict[str, torch.Tensor]] = None
-        self._w: Optional[Dict[str, Any]] = None
-        self._bufs: Dict[Tuple, torch.Tensor] = {}
-
-    # ---------------------------------------------------------------- module-like surface
-    @property
-    def device(self):
-        return self._device
-
-    @property
-    def dtype(self):
-        return self._dtype
-
-    def eval(self):
-        return self
-
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            elif a is not None:
-                device = torch.device(a)
-        if dtype is not None:
-            self._dtype = dtype
-        if device is not None and torch.device(device) != self._device:
-            self._device = torch.device(device)
-            if self._device.type == "cuda" and self._device.index is None:
-                self._device = torch.device("cuda", torch.cuda.current_device())
-            self._w = None
-            self._bufs.clear()
-        return self
 
     def expected_shapes(self) -> Dict[str, Tuple[int, ...]]:
         return dict(_param_shapes(self.config))
 
-    def state_dict(self):
-        return dict(self._sd or {})
-
-    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
-        exp = self.expected_shapes()
-        sd = dict(state_dict)
-        # diffusers < 0.18 names of the mid-block attention
-        for old, new in (("query", "to_q"), ("key", "to_k"), ("value", "to_v"), ("proj_attn", "to_out.0")):
+    def _remap_keys(self, sd):
+        for old, new in (("query", "to_q"), ("key", "to_k"), ("value", "to_v"), ("proj_attn", "to_out.0")):   # diffusers < 0.18 names of the mid-block attention
             for k in list(sd):
                 if f".attentions.0.{old}." in k:
                     sd[k.replace(f".attentions.0.{old}.", f".attentions.0.{new}.")] = sd.pop(k)
-        missing = [k for k in exp if k not in sd]
-        unexpected = [k for k in sd if k not in exp]
-        bad = [k for k in exp if k in sd and tuple(sd[k].shape) != tuple(exp[k]) and sd[k].numel() != math.prod(exp[k])]
-        if bad or (strict and (missing or unexpected)):
-            raise RuntimeError(f"Error(s) in loading state_dict for AutoencoderKL: missing {missing[:6]} unexpected "
-                               f"{unexpected[:6]} size mismatch {bad[:6]}")
-        self._sd = {k: sd[k].detach().to("cpu", torch.float32).reshape(exp[k]) for k in exp if k in sd}
-        self._w = None
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+        return sd
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder: Optional[str] = None, torch_dtype=None, **kwargs):
         d = Path(str(pretrained_model_name_or_path))
         d = d / subfolder if subfolder else d
-        cfg = dict(SD21_VAE_CONFIG)
-        if (d / "config.json").exists():
-            cfg.update({k: v for k, v in json.loads((d / "config.json").read_text()).items() if k in cfg or k.startswith("_")})
-        cfg.update(kwargs)
-        m = cls(**cfg)
-        sd = None
-        if (d / "diffusion_pytorch_model.safetensors").exists():
-            from safetensors.torch import load_file
-            sd = load_file(str(d / "diffusion_pytorch_model.safetensors"))
-        elif (d / "diffusion_pytorch_model.bin").exists():
-            sd = torch.load(str(d / "diffusion_pytorch_model.bin"), map_location="cpu")
+        m = cls(**{**read_config(d, SD21_VAE_CONFIG), **kwargs})
+        sd = read_checkpoint(d, ("diffusion_pytorch_model",))
         if sd is None:
             raise FileNotFoundError(f"no diffusion_pytorch_model.{{safetensors,bin}} under {d}")
         m.load_state_dict(sd)
@@ -164,10 +98,7 @@ class AutoencoderKL(ModuleSurface):
 
     # ---------------------------------------------------------------- packing
     def _pack(self):
-        if self._sd is None:
-            raise RuntimeError("weights not loaded")
-        if self._device.type != "cuda" and not _lib.is_emulator():
-            raise RuntimeError("AutoencoderKL runs on the MI355X only: call .to('cuda')")
+        self._ready()
         sd, dev = self._sd, self._device
         w: Dict[str, Any] = {}
 
@@ -216,8 +147,7 @@ class AutoencoderKL(ModuleSurface):
                 w[f"d.u{i}.r{j}"] = res(f"decoder.up_blocks.{i}.resnets.{j}.")
             if i != len(boc) - 1:
                 p = f"decoder.up_blocks.{i}.upsamplers.0.conv."
-                from .unet import PHASE_UPSAMPLE
-                if PHASE_UPSAMPLE:   # Upsample2D as its phase decomposition (pcdms_amd/unet.py PHASE_UPSAMPLE: 4/9 of the FLOPs; the decoder's sizes are always x2)
+                if unet.PHASE_UPSAMPLE:   # Upsample2D as its phase decomposition (pcdms_amd/unet.py PHASE_UPSAMPLE: 4/9 of the FLOPs; the decoder's sizes are always x2)
                     w[f"d.u{i}.us4"] = ops.pack_upsample_phases(sd[p + "weight"], sd[p + "bias"], dev)
                 else:
                     w[f"d.u{i}.us"] = ops.pack_conv3x3(sd[p + "weight"], sd[p + "bias"], dev)
@@ -229,14 +159,6 @@ class AutoencoderKL(ModuleSurface):
         bout[:oc] = sd["decoder.conv_out.bias"]
         w["d.conv_out"] = ops.pack_conv3x3(wout, bout, dev)
         self._w = w
-
-    def _buf(self, name, shape, dtype=BF16, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self._device)
-            self._bufs[key] = t
-        return t
 
     # ---------------------------------------------------------------- blocks
     def _gn(self, x, B, HW, gb, silu, name):

@@ -4,6 +4,7 @@ checkpoints the reference's drivers read (diffusers ``config.json`` + ``diffusio
 from __future__ import annotations
 
 import json
+from pathlib import Path
 
 import pytest
 import torch
@@ -23,6 +24,12 @@ SD21_UNET_JSON = {
     "mid_block_scale_factor": 1, "norm_eps": 1e-05, "norm_num_groups": 32, "num_class_embeds": None, "only_cross_attention": False,
     "out_channels": 4, "sample_size": 16, "up_block_types": ["UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"],
     "use_linear_projection": True, "upcast_attention": False}
+FRESH = json.loads((Path(__file__).parent / "golden" / "fresh_init_sha256.json").read_text())   # recorded by tests/golden/make_fresh_init_fixture.py
+
+
+def _sha(t):
+    from tests.golden.make_fresh_init_fixture import sha
+    return sha(t)
 
 
 @pytest.mark.parametrize("fmt", ["safetensors", "bin"])
@@ -47,6 +54,8 @@ def test_unet_from_pretrained_like_the_stage2_driver(tmp_path, fmt):
     got = m.state_dict()
     assert got["conv_in.weight"].shape == (64, 9, 3, 3)                                          # re-initialised
     assert got["class_embedding.linear_1.weight"].shape == (256, 64)                             # absent on disk: fresh
+    for k in ("conv_in.weight", "class_embedding.linear_1.weight", "class_embedding.linear_2.bias"):   # the fresh values do not depend on what was loaded
+        assert _sha(got[k]) == FRESH["unet"][k], k
     for k in ("mid_block.resnets.0.conv1.weight", "up_blocks.3.attentions.2.transformer_blocks.0.attn2.to_k.weight", "conv_out.bias"):
         assert torch.equal(got[k], sd[k].float()), k
     # ... then the driver overwrites everything with the trained checkpoint (strict)
@@ -99,6 +108,8 @@ def test_prior_from_pretrained_like_the_stage1_driver(tmp_path):
     assert m.config.embedding_dim == 1024 and m.num_tokens == 6 and got["proj_in.weight"].shape == (128, 1024)
     assert got["positional_embedding"].shape == (1, 6, 128) and "pose_encoder.net.0.weight" in got
     assert torch.equal(got["transformer_blocks.1.ff.net.2.weight"], ours["transformer_blocks.1.ff.net.2.weight"])
+    for k in ("pose_encoder.net.0.weight", "pose_encoder1.net.4.bias", "proj_in.weight", "positional_embedding", "prd_embedding"):
+        assert _sha(got[k]) == FRESH["prior"][k], k                        # fresh: absent on disk or mismatched
     m.load_state_dict(ours)                                                 # then the trained checkpoint, strict (:58-59)
 
 
@@ -135,18 +146,82 @@ def test_scheduler_from_config_of_another_scheduler():
     assert k.config.prediction_type == "sample" and k.config.clip_sample_range == 10.0
 
 
-def test_module_surface_the_drivers_touch():
-    """``.eval() / .half() / .float() / .requires_grad_(False) / .parameters() / .modules()`` on every model object (the drivers chain
-    ``.to(device).eval()``, stage2_batchtest_inpaint_model.py:95-99); training is out of scope and says so."""
-    objs = [P.Stage2_InapintUNet2DConditionModel(**{k: v for k, v in SD21_UNET_JSON.items() if k in ("block_out_channels", "attention_head_dim", "cross_attention_dim")}),
+def test_fresh_init_matches_the_recorded_values(tmp_path):
+    """What ``from_pretrained`` leaves in tensors no checkpoint supplies is pinned bit for bit: SHA-256 of every tensor (one hash over the whole
+    state dict in its order, plus a few by name) against values recorded from the commit before the initialisation moved into
+    ``_module.default_init`` (tests/golden/make_fresh_init_fixture.py)."""
+    from tests.golden.make_fresh_init_fixture import NAMED, digest, fresh_models
+    for name, m in fresh_models(tmp_path):
+        assert digest(m.state_dict(), NAMED[name]) == FRESH[name], name
+        if name == "prior":   # one fan-in rule serves both models only because every multi-dimensional weight the prior draws is 2-D
+            assert all(len(s) <= 2 or k in ("positional_embedding", "prd_embedding") for k, s in m.expected_shapes().items())
+
+
+def _model_objects():
+    return [P.Stage2_InapintUNet2DConditionModel(**{k: v for k, v in SD21_UNET_JSON.items() if k in ("block_out_channels", "attention_head_dim", "cross_attention_dim")}),
             P.AutoencoderKL(block_out_channels=(64, 64, 128, 128)), P.Stage1_PriorTransformer(num_attention_heads=2, num_layers=1, embedding_dim=1024, num_embeddings=2),
             P.Dinov2Model(hidden_size=128, num_hidden_layers=1, num_attention_heads=2), P.CLIPVisionModelWithProjection(hidden_size=128, intermediate_size=128, num_hidden_layers=1, num_attention_heads=2),
             P.ControlNetConditioningEmbedding(64), P.ImageProjModel_p(128, 64, 64)]
+
+
+def test_module_surface_the_drivers_touch():
+    """``.eval() / .half() / .float() / .requires_grad_(False) / .parameters() / .modules()`` on every model object (the drivers chain
+    ``.to(device).eval()``, stage2_batchtest_inpaint_model.py:95-99); training is out of scope and says so."""
+    objs = _model_objects()
     for m in objs:
         assert m.eval() is m and m.requires_grad_(False) is m and m.half() is m and m.float() is m and m.train(False) is m
         assert isinstance(list(m.parameters()), list) and isinstance(list(m.modules()), list)
         with pytest.raises(NotImplementedError):
             m.train()
+        with pytest.raises(NotImplementedError):
+            m.requires_grad_(True)
+        assert list(m.modules()) == [m]
     iproj = objs[-1]
     iproj.load_state_dict({k: torch.zeros(s) for k, s in iproj.expected_shapes().items()})
     assert sum(p.numel() for p in iproj.parameters()) == 128 * 64 + 64 + 2 * 64 + 64 * 64 + 64
+
+
+def test_to_another_device_drops_everything_derived():
+    """``.to(<another device>)`` drops the packed weights, the scratch buffers and the per-class cache of every model object; a dtype-only
+    ``.to`` and a ``.to`` of the device it is on keep them (the buffers' addresses are what a captured graph holds)."""
+    caches = {"_cache": dict(x=1), "_static": ("key",), "_pos_cache": {(1, 1): torch.zeros(1)}}
+    for m in _model_objects():
+        mine = [a for a in caches if hasattr(m, a)]
+        assert m.device == torch.device("cpu") and m._w is None and m._bufs == {}
+        for dev in ("cpu", torch.float16, "meta"):
+            m._w = dict(packed=1)
+            buf = m._buf("x", (2, 3), torch.float32, zero=True)
+            assert m._buf("x", (2, 3), torch.float32) is buf and list(m._bufs) == [("x", (2, 3), torch.float32)]
+            for a in mine:
+                setattr(m, a, type(caches[a])(caches[a]))
+            assert m.to(dev) is m
+            if dev == "meta":
+                assert m.device == torch.device("meta") and m._w is None and m._bufs == {}
+                assert all(not getattr(m, a) for a in mine), mine
+            else:
+                assert m._w == dict(packed=1) and m._bufs and all(getattr(m, a) for a in mine)
+        assert m.dtype == torch.float16
+    assert [hasattr(m, a) for m in _model_objects()[:4] for a in caches].count(True) == 3   # UNet _cache, prior _static, DINOv2 _pos_cache
+
+
+def test_launch_log_ignores_host_tensors():
+    """``ops.LAUNCH_LOG`` times launches with HIP events on the launch stream: under the emulator (CPU tensors) nothing is appended and the
+    call returns the tensor it was given."""
+    from pcdms_amd import _lib, ops
+    from tests.emu import build_emu
+    _lib.use_library(build_emu.load())
+    x = torch.randn(8, 64).to(ops.BF16)
+    pw = ops.pack_linear(torch.randn(64, 64), torch.randn(64), "cpu")
+    g, b = torch.ones(64), torch.zeros(64)
+    before = (ops.LAUNCH_LOG, ops.LAUNCH_KEYS, ops.LAUNCH_SPANS)
+    ops.LAUNCH_LOG, ops.LAUNCH_KEYS, ops.LAUNCH_SPANS = [], [], []
+    try:
+        out, n, o2 = torch.empty(8, 64, dtype=ops.BF16), torch.empty(8, 64, dtype=ops.BF16), torch.empty(8, 64, dtype=ops.BF16)
+        assert ops.layernorm(x, g, b, 1e-5, n) is n
+        assert ops.gemm(x, pw, out) is out
+        assert ops.gemm(x, pw, o2, ln=(g, b, 1e-5), ln_buf=torch.empty(8, 64, dtype=ops.BF16)) is o2
+        assert torch.equal(o2, ops.gemm(n, pw, torch.empty_like(o2)))
+        assert ops.LAUNCH_LOG == [] and ops.LAUNCH_KEYS == []
+        assert ops.LAUNCH_SPANS == [(("ln", 8, 64, 64, ops.EPI_STORE), 0, 0)]   # the pair is recorded, with no launches in it
+    finally:
+        ops.LAUNCH_LOG, ops.LAUNCH_KEYS, ops.LAUNCH_SPANS = before
