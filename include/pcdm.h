@@ -352,6 +352,42 @@ int pcdm_psnr(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, 
 int pcdm_select_image(const void* cand_u8, int N, int Hc, int Wc, const int32_t* win, int channels, const int32_t* index_dev, void* out, int normalized,
                       pcdm_stream_t s);
 
+/* ---- LPIPS v0.1, net = 'alex', eval mode (the second per-pair metric of the paper's protocol; the reference's metrics.py calls the lpips package)
+ * on the device in exact fp32: every convolution is an implicit GEMM on the fp32-input MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain per
+ * output, no bf16 operand anywhere), activations NHWC fp32.  The network is restated from its published definition: scaling layer
+ * (x - shift) / scale with shift = (-.030, -.088, -.188), scale = (.458, .448, .450); AlexNet features conv1 3->64 11x11 s4 p2, MaxPool 3x3 s2, conv2
+ * 64->192 5x5 p2, MaxPool 3x3 s2, conv3 192->384, conv4 384->256, conv5 256->256 (3x3 p1), each with bias + ReLU; per ReLU output l:
+ * n = f / (sqrt(sum_c f^2) + 1e-10), d_l = mean_{h,w} sum_c lin_l[c] (n0 - n1)^2; result sum_l d_l.
+ * pcdm_pack_lpips_conv: HOST loops, fp32 [Cout, Cin, kh, kw] -> fp32 [Kpad / 4][Npad][4] with k = (ky kw + kx) Cp + c, Cp = Cin rounded up to 4
+ *   (conv1: 3 -> 4), Kpad = kh kw Cp rounded up to 16, Npad = Cout rounded up to 16, zeros elsewhere; bias -> fp32 [Npad].  Returns Npad (< 0: bad
+ *   arguments); *K_out = Kpad, *cin_out = Cp; output pointers may be NULL to query sizes.  Upload both.
+ * pcdm_conv2d_f32: out NHWC fp32 [B, Ho, Wo, Cout] = conv(x NHWC fp32 [B, Hi, Wi, Cin], w) + bias, ReLU when relu != 0; Ho = (Hi + 2 pad - kh) / stride
+ *   + 1.  Cin is the PADDED channel count (% 4 == 0), w_packed / bias as pcdm_pack_lpips_conv left them; any kernel size, stride and padding;
+ *   taps outside the image contribute zeros.  Per output the products are accumulated in one fixed k order: reruns are bit-identical and a row's
+ *   result does not depend on where in the batch it lies.  x and w_packed 16-byte aligned.
+ * pcdm_maxpool3s2_f32: MaxPool2d(3, stride 2) without padding (floor) on NHWC fp32, C % 4 == 0, Hi, Wi >= 3.
+ * pcdm_lpips: out[n] (fp32 [N], device) = LPIPS of image n of img0 against image n (ref_n = N) or image 0 (ref_n = 1) of img1; layers (may be
+ *   NULL): fp32 [5, N], the five d_l, whose fp32 sum in tap order is out[n]; argmin (int32, device, may be NULL) = np.argmin(out): the first
+ *   minimum, a NaN ranks as the minimum -- feed it to pcdm_select_image for the best-LPIPS candidate.
+ *   is_f32 = 0: images uint8 NHWC [n, Hi, Wi, 3], x = p / 255; is_f32 = 1: fp32 NCHW [n, 3, Hi, Wi].  normalize != 0: x <- 2 x - 1 (inputs in
+ *   [0, 1]); normalize = 0 feeds x as it is -- on uint8 that is what the reference's LPIPS.calculate_from_disk computes (metrics.py:484-498 hands
+ *   [0, 1] images to a network that expects [-1, 1]; kept, not corrected).  Windows {x0, y0, W, H} (HOST memory) as for pcdm_ssim; W, H >= 31
+ *   (below that the second pool has no window), (N + ref_n) W H < 2^28.  Both images of every pair run as ONE batch of N + ref_n.
+ *   ws: pcdm_lpips_ws_bytes(N, ref_n, H, W) bytes, 16-byte aligned, no initialisation: the activations and 5 N 32 fp64 partial sums.  No atomics,
+ *   no allocation, no host synchronisation; 14 launches on s.  Returns -1 and writes nothing for any argument outside the above. */
+typedef struct pcdm_lpips_weights {
+    const float* conv_w[5];   /* device, pcdm_pack_lpips_conv layout */
+    const float* conv_b[5];   /* device, fp32 [Npad] */
+    const float* lin[5];      /* device, fp32 [64 | 192 | 384 | 256 | 256] */
+} pcdm_lpips_weights;
+int pcdm_pack_lpips_conv(const float* w, const float* bias, int Cout, int Cin, int kh, int kw, float* out_w, float* out_bias, int* K_out, int* cin_out);
+int pcdm_conv2d_f32(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw, int stride, int pad,
+                    int relu, float* out, pcdm_stream_t s);
+int pcdm_maxpool3s2_f32(const float* x, int B, int Hi, int Wi, int C, float* out, pcdm_stream_t s);
+int64_t pcdm_lpips_ws_bytes(int N, int ref_n, int H, int W);
+int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t* win0, const void* img1, int ref_n, int H1, int W1, const int32_t* win1, int is_f32,
+               int normalize, const pcdm_lpips_weights* wts, float* out, float* layers, int32_t* argmin, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+
 /* ---- Input preparation of the evaluation drivers (stage2_batchtest_inpaint_model.py:135-149: Image.resize((W, H), Image.BICUBIC), the
  * [source | black] and [source pose | target pose] canvases, ToTensor + Normalize, CLIPImageProcessor) on the device, from the decoded uint8 pixels.
  * pcdm_resample_u8: Pillow's 8-bit separable resampler.  src uint8 HWC [Hs, Ws, channels] (channels 3 or 1, contiguous) -> the Hd x Wd window at

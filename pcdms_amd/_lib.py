@@ -70,6 +70,12 @@ class UNetConfig(C.Structure):
                 ("freq_shift", C.c_float)]
 
 
+class LpipsWeights(C.Structure):
+    """Mirror of ``pcdm_lpips_weights`` (include/pcdm.h)."""
+
+    _fields_ = [("conv_w", C.c_void_p * 5), ("conv_b", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
 _SIGS = {
@@ -110,6 +116,11 @@ _SIGS = {
     "pcdm_ssim": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _F, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_psnr": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_select_image": ([_P, _I, _I, _I, _W4, _I, _P, _P, _I, _P], C.c_int),
+    "pcdm_pack_lpips_conv": ([_P, _P, _I, _I, _I, _I, _P, _P, _P, _P], C.c_int),
+    "pcdm_conv2d_f32": ([_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_maxpool3s2_f32": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_lpips_ws_bytes": ([_I, _I, _I, _I], _L),
+    "pcdm_lpips": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, C.POINTER(LpipsWeights), _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_resample_ws_bytes": ([_I, _I, _I, _I, _I, _I], _L),
     "pcdm_resample_u8": ([_P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _L, _I, _I, _P, _L, _P], C.c_int),
     "pcdm_u8_to_nchw": ([_P, _I, _I, _I, _W4, _I, C.c_double, C.POINTER(_F), C.POINTER(_F), _P, _P], C.c_int),

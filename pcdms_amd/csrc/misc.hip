@@ -1087,3 +1087,353 @@ extern "C" int pcdm_u8_to_nchw(const void* src_u8, int Hs, int Ws, int channels,
     PCDM_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- LPIPS v0.1, net = 'alex' (the paper's second per-pair metric; the reference's metrics.py goes through the lpips package) in exact fp32 -------
+// scaling layer -> AlexNet features (five convolutions with bias + ReLU, two 3x3 / stride-2 max-pools) -> per tap: channel-normalise both
+// images, squared difference weighted by the 1x1 "lin" layer, spatial mean -> sum of the five taps.  Both images of every pair go through the
+// network as ONE batch (candidates first, then the references: N + ref_n images), so each weight is read once per call.
+// Activations are NHWC fp32.  The convolutions are implicit GEMMs on the fp32-input MFMA (pcdm_device.h: mfma_f32_16x16x4): M = batch Ho Wo,
+// N = Cout, K = kh kw Cin -- a k-ordered fmaf chain per output, no reduced-precision operand anywhere (bf16 operands cost 5e-6 .. 9e-5 of the
+// result, LPIPS differences between methods sit in the third decimal).  No atomics: per-workgroup fp64 partials of the spatial means, added in
+// index order by one last launch, so reruns and batch permutations are bit-identical; an identical pair is exactly 0.
+namespace {
+constexpr int kLpSlices = 32;        // pixel slices per pair and tap of the distance pass
+constexpr int kLpMaxC = 384;         // widest tap (six channels per lane)
+constexpr int kLpChan[5] = {64, 192, 384, 256, 256};
+
+struct LpSrc {             // window origin into uint8 NHWC [n, Hi, Wi, 3] or fp32 NCHW [n, 3, Hi, Wi]
+    const void* p;
+    int Hi, Wi, x0, y0;
+};
+
+// out fp32 NHWC [N + ref_n, H, W, 4] (channel 3 = 0: conv1's Cin padded to one 16-byte fragment) <- the scaling layer of the two windows:
+// x = p / 255 for uint8, 2 x - 1 when normalize, then (x - shift[c]) / scale[c], every step in fp32 (not folded into conv1: other roundings)
+__global__ __launch_bounds__(256) void lpips_input_kernel(LpSrc a, LpSrc b, int N, int f32, int normalize, int W, int H, int64_t total,
+                                                          float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over (image, y, x)
+    if (i >= total) return;
+    const int x = (int)(i % W);
+    const int64_t t = i / W;
+    const int y = (int)(t % H), img = (int)(t / H);
+    const LpSrc s = img < N ? a : b;
+    const int n = img < N ? img : img - N;
+    const int64_t plane = (int64_t)s.Hi * s.Wi, pix = (int64_t)(s.y0 + y) * s.Wi + s.x0 + x;
+    const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = f32 ? ((const float*)s.p)[((int64_t)n * 3 + c) * plane + pix] : (float)((const uint8_t*)s.p)[((int64_t)n * plane + pix) * 3 + c] / 255.0f;
+        if (normalize) v = 2.0f * v - 1.0f;
+        o[c] = (v - shift[c]) / scale[c];
+    }
+    *(f32x4*)(out + i * 4) = o;
+}
+
+struct ConvF32 {
+    const float* x;        // NHWC [B, Hi, Wi, Cin], Cin % 4 == 0
+    const float* w;        // packed [Kpad / 4][Npad][4] (pcdm_pack_lpips_conv), k = (ky kw + kx) Cin + c
+    const float* bias;     // [Npad]
+    float* out;            // NHWC [B, Ho, Wo, Cout]
+    int Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad, Kpad, M, relu;
+};
+
+// One wave = a 32 x 64 output tile (2 x 4 accumulators of 16 x 16: eight independent MFMA chains), four waves along M per workgroup, operands
+// straight from global memory / L2 (the whole LPIPS call is a few GFLOP; no LDS stage).  Per 16 k: lane (r, g) loads the 16 bytes
+// k0 + 4g .. + 3 of its two rows' patches -- Cin % 4 == 0, so a fragment never straddles a tap and an out-of-image tap is one zero fragment,
+// not a clamped read -- and of its four weight columns, then runs four MFMA steps per accumulator (mfma_f32_16x16x4_quad).
+// The tap (ky, kx, c) of a lane advances by 16 channels per step without a division.  M and N tails: rows >= M load zeros and are not stored,
+// 16-column sub-tiles beyond Npad and the second row block of a tile that ends in the first are skipped (wave-uniform).
+__global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const int m0 = (blockIdx.x * 4 + wave) * 32, n0 = blockIdx.y * 64;
+    if (m0 >= p.M) return;
+    const int nsub = imin(4, (p.Npad - n0) / 16);
+    const bool two = m0 + 16 < p.M;
+    const float* xb[2];
+    int iy0[2], ix0[2];
+    bool valid[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int m = m0 + 16 * t + r;
+        valid[t] = m < p.M;
+        const int mm = valid[t] ? m : 0;
+        const int b = mm / (p.Ho * p.Wo), q = mm - b * p.Ho * p.Wo;
+        const int oy = q / p.Wo, ox = q - oy * p.Wo;
+        iy0[t] = oy * p.stride - p.pad;
+        ix0[t] = ox * p.stride - p.pad;
+        xb[t] = p.x + (int64_t)b * p.Hi * p.Wi * p.Cin;
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int c = 4 * g, kx = 0, ky = 0;
+    while (c >= p.Cin) {
+        c -= p.Cin;
+        if (++kx == p.kw) { kx = 0; ++ky; }
+    }
+    const float* wp = p.w + ((int64_t)g * p.Npad + n0 + r) * 4;
+    for (int k0 = 0; k0 < p.Kpad; k0 += 16) {
+        f32x4 a[2], b[4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int iy = iy0[t] + ky, ix = ix0[t] + kx;
+            const bool ok = valid[t] && ky < p.kh && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
+            a[t] = ok ? *(const f32x4*)(xb[t] + ((int64_t)iy * p.Wi + ix) * p.Cin + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = j < nsub ? *(const f32x4*)(wp + j * 64) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nsub) {
+                acc[0][j] = mfma_f32_16x16x4_quad(a[0], b[j], acc[0][j]);
+                if (two) acc[1][j] = mfma_f32_16x16x4_quad(a[1], b[j], acc[1][j]);
+            }
+        wp += (int64_t)16 * p.Npad;
+        c += 16;
+        while (c >= p.Cin) {
+            c -= p.Cin;
+            if (++kx == p.kw) { kx = 0; ++ky; }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + 16 * j + r;
+        if (j >= nsub || n >= p.Cout) continue;
+        const float bv = p.bias[n];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int m = m0 + 16 * t + 4 * g + e;
+                if (m >= p.M) continue;
+                float v = acc[t][j][e] + bv;
+                if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
+                p.out[(int64_t)m * p.Cout + n] = v;
+            }
+    }
+}
+
+// MaxPool2d(3, stride 2), no padding, floor: every window lies inside the image.  NHWC fp32, four channels per lane.
+__global__ __launch_bounds__(256) void maxpool3s2_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int Hi, int Wi, int Ho, int Wo, int C4,
+                                                             int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over (b, oy, ox, c / 4)
+    if (i >= total) return;
+    const int c4 = (int)(i % C4);
+    int64_t t = i / C4;
+    const int ox = (int)(t % Wo);
+    t /= Wo;
+    const int oy = (int)(t % Ho), b = (int)(t / Ho);
+    const f32x4* src = (const f32x4*)x + (((int64_t)b * Hi + 2 * oy) * Wi + 2 * ox) * C4 + c4;
+    f32x4 m = src[0];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const f32x4 v = src[((int64_t)dy * Wi + dx) * C4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = v[e] > m[e] || v[e] != v[e] ? v[e] : m[e];
+        }
+    ((f32x4*)out)[i] = m;
+}
+
+// One tap: part[n * kLpSlices + slice] = sum over the slice's pixels of sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, f0 = image n,
+// f1 = image N + (ref_n == 1 ? 0 : n) of the NHWC features [N + ref_n, P, C].  A wave per pixel: channels across the lanes, fp32 inside the
+// pixel (as the network), the pixels of a wave added in fp64 in pixel order.
+__global__ __launch_bounds__(256) void lpips_dist_kernel(const float* __restrict__ f, int N, int ref_n, int P, int C, const float* __restrict__ lin,
+                                                         double* __restrict__ part) {
+    __shared__ double red[4];
+    const int n = blockIdx.y, sl = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per = (P + kLpSlices - 1) / kLpSlices;
+    const int pa = sl * per, pb = imin(P, pa + per);
+    const float* f0 = f + (int64_t)n * P * C;
+    const float* f1 = f + (int64_t)(N + (ref_n == 1 ? 0 : n)) * P * C;
+    double acc = 0.0;
+    for (int px = pa + wave; px < pb; px += 4) {
+        float v0[kLpMaxC / 64], v1[kLpMaxC / 64], s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < kLpMaxC / 64; ++j) {
+            const int c = lane + 64 * j;
+            v0[j] = c < C ? f0[(int64_t)px * C + c] : 0.f;
+            v1[j] = c < C ? f1[(int64_t)px * C + c] : 0.f;
+            s0 += v0[j] * v0[j];
+            s1 += v1[j] * v1[j];
+        }
+        const float d0 = sqrtf(wave_sum(s0)) + 1e-10f, d1 = sqrtf(wave_sum(s1)) + 1e-10f;
+        float tsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < kLpMaxC / 64; ++j) {
+            const int c = lane + 64 * j;
+            const float e = v0[j] / d0 - v1[j] / d1;
+            if (c < C) tsum += lin[c] * (e * e);
+        }
+        acc += (double)wave_sum(tsum);
+    }
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(int64_t)n * kLpSlices + sl] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// layers[l * N + n] = float(sum of the slices in index order / pixels of tap l); out[n] = their fp32 sum in tap order (as the lpips package adds
+// its five fp32 maps); then np.argmin: the first minimum wins and a NaN ranks as the minimum
+struct LpCounts { double px[5]; };
+__global__ __launch_bounds__(256) void lpips_final_kernel(const double* __restrict__ part, int N, LpCounts cnt, float* __restrict__ out,
+                                                          float* __restrict__ layers, int32_t* __restrict__ argmin) {
+    for (int n = threadIdx.x; n < N; n += 256) {
+        float tot = 0.f;
+        for (int l = 0; l < 5; ++l) {
+            double s = 0.0;
+            for (int i = 0; i < kLpSlices; ++i) s += part[((int64_t)l * N + n) * kLpSlices + i];
+            const float d = (float)(s / cnt.px[l]);
+            if (layers) layers[l * N + n] = d;
+            tot += d;
+        }
+        out[n] = tot;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && argmin) {
+        int best = 0;
+        float vb = out[0];
+        for (int i = 1; i < N && vb == vb; ++i) {
+            const float v = out[i];
+            if (v != v || v < vb) { best = i; vb = v; }
+        }
+        *argmin = best;
+    }
+}
+
+struct LpGeom { int h[5], w[5], hp[2], wp[2]; };   // the five taps' sizes; the two pooled sizes
+inline bool lpips_geom(int H, int W, LpGeom* g) {
+    if (H < 31 || W < 31) return false;               // below 31 the second pool has no 3 x 3 window left
+    g->h[0] = (H + 4 - 11) / 4 + 1;  g->w[0] = (W + 4 - 11) / 4 + 1;
+    g->hp[0] = (g->h[0] - 3) / 2 + 1; g->wp[0] = (g->w[0] - 3) / 2 + 1;
+    g->h[1] = g->hp[0];              g->w[1] = g->wp[0];
+    g->hp[1] = (g->h[1] - 3) / 2 + 1; g->wp[1] = (g->w[1] - 3) / 2 + 1;
+    for (int l = 2; l < 5; ++l) { g->h[l] = g->hp[1]; g->w[l] = g->wp[1]; }
+    return true;
+}
+inline int64_t lp_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+// workspace: [input B H W 4 | tap 1..5 | pool 1, 2 | partials 5 N kLpSlices fp64], each a multiple of 256 bytes; offsets in bytes
+struct LpLayout { int64_t in, tap[5], pool[2], part, total; };
+inline LpLayout lpips_layout(int N, int ref_n, int H, int W, const LpGeom& g) {
+    const int64_t B = N + ref_n;
+    LpLayout o;
+    int64_t at = 0;
+    o.in = at;  at += lp_align(B * H * W * 4 * (int64_t)sizeof(float));
+    for (int l = 0; l < 5; ++l) { o.tap[l] = at; at += lp_align(B * g.h[l] * g.w[l] * kLpChan[l] * (int64_t)sizeof(float)); }
+    for (int i = 0; i < 2; ++i) { o.pool[i] = at; at += lp_align(B * g.hp[i] * g.wp[i] * kLpChan[i] * (int64_t)sizeof(float)); }
+    o.part = at; at += lp_align((int64_t)5 * N * kLpSlices * (int64_t)sizeof(double));
+    o.total = at;
+    return o;
+}
+inline bool lpips_sizes_ok(int N, int ref_n, int H, int W) {
+    return N > 0 && N <= 65535 && (ref_n == 1 || ref_n == N) && H > 0 && W > 0 && (int64_t)(N + ref_n) * H * W < (int64_t)1 << 28;
+}
+
+inline int conv_f32_launch(const float* x, int B, int Hi, int Wi, int Cin, const float* w, const float* bias, int Cout, int kh, int kw, int stride,
+                           int pad, int relu, float* out, hipStream_t s) {
+    if (!x || !w || !bias || !out || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 4 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return -1;
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return -1;
+    const int Ho = (Hi + 2 * pad - kh) / stride + 1, Wo = (Wi + 2 * pad - kw) / stride + 1;
+    if (Hi + 2 * pad < kh || Wi + 2 * pad < kw) return -1;
+    const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
+    const int Npad = (Cout + 15) / 16 * 16;
+    if (M * Cout >= (int64_t)1 << 31 || (int64_t)B * Hi * Wi * Cin >= (int64_t)1 << 31 || K >= 1 << 24 || (Npad + 63) / 64 > 65535) return -1;
+    ConvF32 p{x, w, bias, out, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad, (int)((K + 15) / 16 * 16), (int)M, relu};
+    PCDM_LAUNCH(conv_f32_kernel, dim3((unsigned)((M + 127) / 128), (Npad + 63) / 64), dim3(256), 0, s, p);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+inline int maxpool_f32_launch(const float* x, int B, int Hi, int Wi, int C, float* out, hipStream_t s) {
+    if (!x || !out || B <= 0 || Hi < 3 || Wi < 3 || C <= 0 || C % 4 || (((uintptr_t)x | (uintptr_t)out) & 15)) return -1;
+    if ((int64_t)B * Hi * Wi * C >= (int64_t)1 << 31) return -1;
+    const int Ho = (Hi - 3) / 2 + 1, Wo = (Wi - 3) / 2 + 1;
+    const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
+    PCDM_LAUNCH(maxpool3s2_f32_kernel, grid1d(total, 256), dim3(256), 0, s, x, out, Hi, Wi, Ho, Wo, C / 4, total);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+extern "C" int pcdm_pack_lpips_conv(const float* w, const float* bias, int Cout, int Cin, int kh, int kw, float* out_w, float* out_bias, int* K_out,
+                                    int* cin_out) {
+    if (Cout <= 0 || Cin <= 0 || kh <= 0 || kw <= 0) return -1;
+    const int Cp = (Cin + 3) / 4 * 4, Npad = (Cout + 15) / 16 * 16;
+    const int64_t K = (int64_t)kh * kw * Cp, Kpad = (K + 15) / 16 * 16;
+    if (K >= 1 << 24) return -1;
+    if (K_out) *K_out = (int)Kpad;
+    if (cin_out) *cin_out = Cp;
+    if (out_w) {
+        if (!w) return -1;
+        for (int64_t i = 0; i < Kpad * Npad; ++i) out_w[i] = 0.f;
+        for (int64_t n = 0; n < Cout; ++n)
+            for (int c = 0; c < Cin; ++c)
+                for (int t = 0; t < kh * kw; ++t) {
+                    const int64_t k = (int64_t)t * Cp + c;
+                    out_w[((k / 4) * Npad + n) * 4 + (k & 3)] = w[(n * Cin + c) * kh * kw + t];
+                }
+    }
+    if (out_bias)
+        for (int n = 0; n < Npad; ++n) out_bias[n] = (bias && n < Cout) ? bias[n] : 0.f;
+    return Npad;
+}
+
+extern "C" int pcdm_conv2d_f32(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw,
+                               int stride, int pad, int relu, float* out, pcdm_stream_t s) {
+    return conv_f32_launch(x, B, Hi, Wi, Cin, w_packed, bias, Cout, kh, kw, stride, pad, relu, out, (hipStream_t)s);
+}
+
+extern "C" int pcdm_maxpool3s2_f32(const float* x, int B, int Hi, int Wi, int C, float* out, pcdm_stream_t s) {
+    return maxpool_f32_launch(x, B, Hi, Wi, C, out, (hipStream_t)s);
+}
+
+extern "C" int64_t pcdm_lpips_ws_bytes(int N, int ref_n, int H, int W) {
+    LpGeom g;
+    if (!lpips_sizes_ok(N, ref_n, H, W) || !lpips_geom(H, W, &g)) return -1;
+    return lpips_layout(N, ref_n, H, W, g).total;
+}
+
+extern "C" int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t* win0, const void* img1, int ref_n, int H1, int W1,
+                          const int32_t* win1, int is_f32, int normalize, const pcdm_lpips_weights* wts, float* out, float* layers, int32_t* argmin,
+                          void* ws, int64_t ws_bytes, pcdm_stream_t s) {
+    if (!img0 || !img1 || !wts || !out || !ws || ((uintptr_t)ws & 15)) return -1;
+    if (!met_window_ok(H0, W0, win0) || !met_window_ok(H1, W1, win1) || win0[2] != win1[2] || win0[3] != win1[3]) return -1;
+    const int W = win0[2], H = win0[3], B = N + ref_n;
+    LpGeom g;
+    if (!lpips_sizes_ok(N, ref_n, H, W) || !lpips_geom(H, W, &g)) return -1;
+    if ((int64_t)N * H0 * W0 * 3 >= (int64_t)1 << 31 || (int64_t)ref_n * H1 * W1 * 3 >= (int64_t)1 << 31) return -1;
+    for (int l = 0; l < 5; ++l)
+        if (!wts->conv_w[l] || !wts->conv_b[l] || !wts->lin[l]) return -1;
+    const LpLayout lay = lpips_layout(N, ref_n, H, W, g);
+    if (ws_bytes < lay.total) return -1;
+    char* base = (char*)ws;
+    float* x = (float*)(base + lay.in);
+    float* tap[5];
+    for (int l = 0; l < 5; ++l) tap[l] = (float*)(base + lay.tap[l]);
+    float* pool[2] = {(float*)(base + lay.pool[0]), (float*)(base + lay.pool[1])};
+    double* part = (double*)(base + lay.part);
+    hipStream_t st = (hipStream_t)s;
+    const int64_t total = (int64_t)B * H * W;
+    PCDM_LAUNCH(lpips_input_kernel, grid1d(total, 256), dim3(256), 0, st, LpSrc{img0, H0, W0, win0[0], win0[1]}, LpSrc{img1, H1, W1, win1[0], win1[1]}, N,
+                is_f32, normalize, W, H, total, x);
+    PCDM_CHECK_LAUNCH();
+    int rc = conv_f32_launch(x, B, H, W, 4, wts->conv_w[0], wts->conv_b[0], 64, 11, 11, 4, 2, 1, tap[0], st);
+    if (rc == 0) rc = maxpool_f32_launch(tap[0], B, g.h[0], g.w[0], 64, pool[0], st);
+    if (rc == 0) rc = conv_f32_launch(pool[0], B, g.hp[0], g.wp[0], 64, wts->conv_w[1], wts->conv_b[1], 192, 5, 5, 1, 2, 1, tap[1], st);
+    if (rc == 0) rc = maxpool_f32_launch(tap[1], B, g.h[1], g.w[1], 192, pool[1], st);
+    if (rc == 0) rc = conv_f32_launch(pool[1], B, g.hp[1], g.wp[1], 192, wts->conv_w[2], wts->conv_b[2], 384, 3, 3, 1, 1, 1, tap[2], st);
+    if (rc == 0) rc = conv_f32_launch(tap[2], B, g.h[2], g.w[2], 384, wts->conv_w[3], wts->conv_b[3], 256, 3, 3, 1, 1, 1, tap[3], st);
+    if (rc == 0) rc = conv_f32_launch(tap[3], B, g.h[3], g.w[3], 256, wts->conv_w[4], wts->conv_b[4], 256, 3, 3, 1, 1, 1, tap[4], st);
+    if (rc != 0) return rc;
+    LpCounts cnt;
+    for (int l = 0; l < 5; ++l) {
+        cnt.px[l] = (double)g.h[l] * (double)g.w[l];
+        PCDM_LAUNCH(lpips_dist_kernel, dim3(kLpSlices, N), dim3(256), 0, st, tap[l], N, ref_n, g.h[l] * g.w[l], kLpChan[l], wts->lin[l],
+                    part + (int64_t)l * N * kLpSlices);
+        PCDM_CHECK_LAUNCH();
+    }
+    PCDM_LAUNCH(lpips_final_kernel, dim3(1), dim3(256), 0, st, part, N, cnt, out, layers, argmin);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}

@@ -279,6 +279,52 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(u16x8 a, u16x8 b, f32x4 c) {
 #endif
 }
 
+// 16x16x4 f32 (v_mfma_f32_16x16x4_f32: fp32 operands, exact):  A lane l -> row (l&15), k = l>>4 ;  B lane l -> col (l&15), same k ; ONE
+//                 float each;  D as 16x16x32: lane l, reg r -> col (l&15), row r + 4*(l>>4).  The hardware's result is bit for bit the
+//                 k-ordered chain d = fmaf(a_k, b_k, d), k = 0..3, starting from c -- which is what the emulated branch computes.
+__device__ __forceinline__ f32x4 mfma_f32_16x16x4(float a, float b, f32x4 c) {
+#ifdef PCDM_EMU
+    struct P { float a, b; } p = {a, b};
+    const char* all = emu::wave_exchange(&p, sizeof(p));
+    const int l = emu::lane_id(), j = l & 15, hh = l >> 4;
+    f32x4 d = c;
+    for (int r = 0; r < 4; ++r) {
+        const int i = r + 4 * hh;
+        float s = c[r];
+        for (int k = 0; k < 4; ++k) s = fmaf(((const P*)(all + (i + 16 * k) * emu::kSlot))->a, ((const P*)(all + (j + 16 * k) * emu::kSlot))->b, s);
+        d[r] = s;
+    }
+    return d;
+#else
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+#endif
+}
+// Four of them over four-element fragments (one 16-byte load per operand and lane): step e takes element e of every lane, so with lane group
+// g = l>>4 holding k = 4g .. 4g+3 the chain runs over k = e, 4 + e, 8 + e, 12 + e for e = 0..3 -- a fixed order, the same on both branches
+// (the emulator pays one wave rendezvous for the four steps).
+__device__ __forceinline__ f32x4 mfma_f32_16x16x4_quad(f32x4 a, f32x4 b, f32x4 c) {
+#ifdef PCDM_EMU
+    struct P { float a[4], b[4]; } p;
+    for (int e = 0; e < 4; ++e) { p.a[e] = a[e]; p.b[e] = b[e]; }
+    const char* all = emu::wave_exchange(&p, sizeof(p));
+    const int l = emu::lane_id(), j = l & 15, hh = l >> 4;
+    f32x4 d = c;
+    for (int r = 0; r < 4; ++r) {
+        const int i = r + 4 * hh;
+        float s = c[r];
+        for (int e = 0; e < 4; ++e)
+            for (int k = 0; k < 4; ++k)
+                s = fmaf(((const P*)(all + (i + 16 * k) * emu::kSlot))->a[e], ((const P*)(all + (j + 16 * k) * emu::kSlot))->b[e], s);
+        d[r] = s;
+    }
+    return d;
+#else
+#pragma unroll
+    for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], c, 0, 0, 0);
+    return c;
+#endif
+}
+
 // ---- OCP fp8 e4m3 (gfx950: e4m3fn -- bias 7, max 448, no infinities; NOT MI300's fnuz) --------------------------------------
 // decode / encode on the host side of the emulator and in tests; the GPU converts with v_cvt_pk_fp8_f32 (RNE)
 __device__ __forceinline__ float fp8_e4m3_to_f(uint32_t v) {

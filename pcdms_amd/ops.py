@@ -963,6 +963,76 @@ def select_image(cand: torch.Tensor, win: Sequence[int], index: torch.Tensor, ou
     return out
 
 
+# ------------------------------------------------------------------------------------ LPIPS (pcdms_amd/metrics.py: LPIPS is the public surface)
+def pack_lpips_conv(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> dict:
+    """fp32 [Cout, Cin, kh, kw] (+ bias [Cout]) -> the packed fp32 operand of ``conv2d_f32`` on ``device`` (include/pcdm.h: pcdm_pack_lpips_conv):
+    ``{"w", "bias", "cout", "cin" (padded to 4), "kh", "kw"}``."""
+    assert w.dim() == 4, w.shape
+    w = w.detach().to("cpu", torch.float32).contiguous()
+    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
+    Cout, Cin, kh, kw = (int(v) for v in w.shape)
+    assert b is None or tuple(b.shape) == (Cout,), (b.shape, Cout)
+    K, cp = C.c_int(0), C.c_int(0)
+    lib = _lib.lib()
+    Npad = lib.pcdm_pack_lpips_conv(None, None, Cout, Cin, kh, kw, None, None, C.byref(K), C.byref(cp))
+    if Npad < 0:
+        raise RuntimeError(f"pcdm_pack_lpips_conv refuses {tuple(w.shape)}")
+    pw, pb = torch.empty(K.value * Npad, dtype=torch.float32), torch.empty(Npad, dtype=torch.float32)
+    _chk(min(0, lib.pcdm_pack_lpips_conv(_ptr(w), _ptr(b), Cout, Cin, kh, kw, _ptr(pw), _ptr(pb), None, None)), "pcdm_pack_lpips_conv")
+    return {"w": pw.to(device), "bias": pb.to(device), "cout": Cout, "cin": cp.value, "kh": kh, "kw": kw}
+
+
+def conv2d_f32(x: torch.Tensor, pw: dict, *, stride: int = 1, pad: int = 0, relu: bool = False) -> torch.Tensor:
+    """x NHWC fp32 [B, Hi, Wi, pw["cin"]] -> NHWC fp32 [B, Ho, Wo, Cout]: exact-fp32 implicit-GEMM convolution + bias (+ ReLU) on the fp32-input
+    MFMA (include/pcdm.h: pcdm_conv2d_f32)."""
+    _c(x, torch.float32)
+    B, Hi, Wi, Cin = (int(v) for v in x.shape)
+    assert Cin == pw["cin"], (Cin, pw["cin"])
+    Ho, Wo = (Hi + 2 * pad - pw["kh"]) // stride + 1, (Wi + 2 * pad - pw["kw"]) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"a {pw['kh']} x {pw['kw']} kernel does not fit a {Hi} x {Wi} image padded by {pad}")
+    out = torch.empty((B, Ho, Wo, pw["cout"]), dtype=torch.float32, device=x.device)
+    _chk(_lib.lib().pcdm_conv2d_f32(_ptr(x), B, Hi, Wi, Cin, _ptr(pw["w"]), _ptr(pw["bias"]), pw["cout"], pw["kh"], pw["kw"], int(stride), int(pad),
+                                    int(relu), _ptr(out), _stream(x)), "pcdm_conv2d_f32")
+    return out
+
+
+def maxpool3s2_f32(x: torch.Tensor) -> torch.Tensor:
+    """MaxPool2d(3, stride 2), no padding, on NHWC fp32 (include/pcdm.h: pcdm_maxpool3s2_f32)."""
+    _c(x, torch.float32)
+    B, Hi, Wi, Cn = (int(v) for v in x.shape)
+    if Hi < 3 or Wi < 3:
+        raise ValueError(f"no 3 x 3 window in a {Hi} x {Wi} image")
+    out = torch.empty((B, (Hi - 3) // 2 + 1, (Wi - 3) // 2 + 1, Cn), dtype=torch.float32, device=x.device)
+    _chk(_lib.lib().pcdm_maxpool3s2_f32(_ptr(x), B, Hi, Wi, Cn, _ptr(out), _stream(x)), "pcdm_maxpool3s2_f32")
+    return out
+
+
+def lpips_ws_bytes(N: int, ref_n: int, H: int, W: int) -> int:
+    """Workspace bytes of ``lpips``; -1: the library refuses the problem (sides below 31 among others)."""
+    return int(_lib.lib().pcdm_lpips_ws_bytes(N, ref_n, H, W))
+
+
+def lpips(img0: torch.Tensor, img1: torch.Tensor, win0: Sequence[int], win1: Sequence[int], weights: "_lib.LpipsWeights", out: torch.Tensor,
+          layers: Optional[torch.Tensor], argmin: Optional[torch.Tensor], ws: torch.Tensor, *, normalize: bool) -> torch.Tensor:
+    """img0 / img1 uint8 NHWC [n, Hi, Wi, 3] or fp32 NCHW [n, 3, Hi, Wi] (both the same), img1 with batch 1 or img0's; out fp32 [N], layers fp32
+    [5, N] or None, argmin int32 [1] or None (include/pcdm.h: pcdm_lpips)."""
+    assert img0.dim() == 4 and img1.dim() == 4 and img0.dtype == img1.dtype and img0.dtype in (torch.uint8, torch.float32)
+    assert img0.is_contiguous() and img1.is_contiguous() and img0.device == img1.device
+    f32 = int(img0.dtype == torch.float32)
+    (H0, W0), (H1, W1) = (img0.shape[2:], img1.shape[2:]) if f32 else (img0.shape[1:3], img1.shape[1:3])
+    assert (img0.shape[1] if f32 else img0.shape[3]) == 3 and (img1.shape[1] if f32 else img1.shape[3]) == 3, (img0.shape, img1.shape)
+    _c(out, torch.float32)
+    if layers is not None:
+        _c(layers, torch.float32)
+    if argmin is not None:
+        _c(argmin, torch.int32)
+    _chk(_lib.lib().pcdm_lpips(_ptr(img0), img0.shape[0], int(H0), int(W0), _win(win0), _ptr(img1), img1.shape[0], int(H1), int(W1), _win(win1), f32,
+                               int(normalize), C.byref(weights), _ptr(out), _ptr(layers), _ptr(argmin), _ptr(ws), ws.numel() * ws.element_size(),
+                               _stream(img0)), "pcdm_lpips")
+    return out
+
+
 # ------------------------------------------------------------------------------------ input preparation (pcdms_amd/preprocess.py is the public surface)
 def resample_ws_bytes(Hs: int, Ws: int, Hd: int, Wd: int, channels: int, ky: int) -> int:
     """Workspace bytes of ``resample_u8`` (0: one launch, no workspace); -1: the library refuses the problem."""

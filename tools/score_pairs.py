@@ -1,0 +1,92 @@
+"""Score two sets of equal-sized images pair by pair on the device: PSNR, Gaussian-weighted SSIM and LPIPS (AlexNet), printed the way the
+reference's ``Reconstruction_Metrics.calculate_from_disk`` / ``LPIPS.calculate_from_disk`` print them (means and variances over the pairs).
+
+    python tools/score_pairs.py GENERATED_DIR GT_DIR --lpips-weights alex_lpips.pth [--lpips-lin alex.pth] [--normalize]
+
+Each argument is a directory (its image files, sorted by name), a ``.txt`` list of paths, or one image file.  Files are decoded with PIL and
+scored AS THEY ARE: the images of a pair, and all pairs, must have one size.  The reference resizes every image with
+``cv2.resize(..., INTER_CUBIC)`` first; that resampler is NOT restated here -- OpenCV is not a dependency of this project and its output could
+not be checked -- so resize beforehand if the files are not at the evaluation size (``pcdms_amd.preprocess`` has Pillow's resampler on the device).
+SSIM is the reference's ``ssim_256`` (sigma 1.2, data range = max - min of the generated image); LPIPS follows the reference in feeding [0, 1]
+images without the [-1, 1] remap unless ``--normalize`` is given (pcdms_amd/metrics.py: LPIPS).  FID is out of scope.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+IMAGE_SUFFIXES = {".png", ".jpg", ".jpeg", ".bmp", ".webp"}
+
+
+def image_list(arg: str) -> list:
+    p = Path(arg)
+    if p.is_dir():
+        return sorted(str(f) for f in p.iterdir() if f.suffix.lower() in IMAGE_SUFFIXES)
+    if p.suffix.lower() == ".txt":
+        return sorted(ln.strip() for ln in p.read_text().splitlines() if ln.strip())
+    return [str(p)]
+
+
+def load_batch(files, device) -> torch.Tensor:
+    from PIL import Image
+    arrs = [np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in files]
+    if len({a.shape for a in arrs}) != 1:
+        raise ValueError(f"images of different sizes: {sorted({a.shape[:2] for a in arrs})} (resize them first; see --help)")
+    return torch.from_numpy(np.stack(arrs)).to(device)
+
+
+def score(files_a, files_b, lpips_model, device, *, normalize: bool = False, batch: int = 16) -> dict:
+    """Per-pair fp32 arrays ``{"psnr", "ssim_256", "lpips"}`` (``lpips`` only with a model)."""
+    from pcdms_amd import metrics
+    if len(files_a) != len(files_b) or not files_a:
+        raise ValueError(f"{len(files_a)} generated images against {len(files_b)} ground-truth images")
+    res = {"psnr": [], "ssim_256": []}
+    if lpips_model is not None:
+        res["lpips"] = []
+    for i in range(0, len(files_a), batch):
+        a, b = load_batch(files_a[i:i + batch], device), load_batch(files_b[i:i + batch], device)
+        if a.shape != b.shape:
+            raise ValueError(f"generated images {tuple(a.shape[1:3])}, ground truth {tuple(b.shape[1:3])}")
+        res["psnr"].append(metrics.psnr(a, b))
+        res["ssim_256"].append(metrics.ssim(a, b))
+        if lpips_model is not None:
+            res["lpips"].append(lpips_model(a, b, normalize=normalize)[:, 0, 0, 0])
+    return {k: torch.cat(v).cpu().numpy() for k, v in res.items()}
+
+
+def report(res: dict) -> str:
+    lines = ["PSNR: %.4f PSNR Variance: %.4f SSIM_256: %.4f SSIM_256 Variance: %.4f" % (
+        round(float(np.mean(res["psnr"])), 4), round(float(np.var(res["psnr"])), 4), round(float(np.mean(res["ssim_256"])), 4),
+        round(float(np.var(res["ssim_256"])), 4))]
+    if "lpips" in res:
+        lines.append("lpips: %.3f lpips Variance: %.4f" % (float(np.mean(res["lpips"])), round(float(np.var(res["lpips"])), 4)))
+    return "\n".join(lines)
+
+
+def main(argv=None, device=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("generated")
+    ap.add_argument("ground_truth")
+    ap.add_argument("--lpips-weights", help="LPIPS checkpoint (.pth / .safetensors): the lpips package's layout, or torchvision's alexnet with --lpips-lin")
+    ap.add_argument("--lpips-lin", help="the lpips package's alex.pth (lin layers) when --lpips-weights is torchvision's alexnet")
+    ap.add_argument("--normalize", action="store_true", help="map [0, 1] to [-1, 1] before LPIPS (the reference's evaluation does not)")
+    ap.add_argument("--batch", type=int, default=16)
+    args = ap.parse_args(argv)
+    from pcdms_amd import metrics
+    device = torch.device("cuda:0") if device is None else device
+    model = metrics.LPIPS.from_pretrained(args.lpips_weights, args.lpips_lin) if args.lpips_weights else None
+    res = score(image_list(args.generated), image_list(args.ground_truth), model, device, normalize=args.normalize, batch=args.batch)
+    print(report(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()
