@@ -388,6 +388,59 @@ int64_t pcdm_lpips_ws_bytes(int N, int ref_n, int H, int W);
 int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t* win0, const void* img1, int ref_n, int H1, int W1, const int32_t* win1, int is_f32,
                int normalize, const pcdm_lpips_weights* wts, float* out, float* layers, int32_t* argmin, void* ws, int64_t ws_bytes, pcdm_stream_t s);
 
+/* ---- FID (the third metric of the paper's protocol; the reference's metrics.py:23-257 and inception.py) on the device: torchvision's InceptionV3
+ * trunk in exact fp32 on the same fp32-input MFMA convolution as LPIPS, fp64 statistics, mean and covariance.  The Frechet distance itself is host
+ * fp64 (pcdms_amd/metrics.py: frechet_distance).  Restated from the published definition; torchvision is not a dependency.
+ * pcdm_conv2d_f32_ex: pcdm_conv2d_f32 with a padding per axis (Ho = (Hi + 2 pad_h - kh) / stride + 1, Wo likewise with pad_w: the 1 x 7 / 7 x 1 /
+ *   1 x 3 / 3 x 1 kernels) and an output slice: out is an NHWC tensor with out_pitch channels per pixel and the Cout results of a pixel go to its
+ *   channels [out_offset, out_offset + Cout); no other byte of out is written, so the branches of an Inception block write the concatenated tensor
+ *   directly.  0 <= out_offset <= out_pitch - Cout, B Ho Wo out_pitch < 2^31.  Same packed weights (pcdm_pack_lpips_conv), same k order: with pad_h
+ *   = pad_w, out_pitch = Cout, out_offset = 0 the result equals pcdm_conv2d_f32's bit for bit.
+ * pcdm_maxpool3s2_f32_ex: pcdm_maxpool3s2_f32 into the channels [out_offset, out_offset + C) of an out_pitch-channel tensor (both % 4 == 0).
+ * pcdm_avgpool3_f32: F.avg_pool2d(x, 3, 1, 1) (count_include_pad) on NHWC fp32, C % 4 == 0: the nine taps added in (dy, dx) order in fp32, zeros
+ *   outside the image, the sum divided by 9.
+ * pcdm_global_avgpool_f32: out[b, c] (fp32 [B, C]) = mean over the P pixels of NHWC fp32 [B, P, C]: pixel order, fp64 sum, rounded once.
+ * pcdm_inception_input: out fp32 NHWC [N, Ho, Wo, 4] (channel 3 = 0) <- the window {x0, y0, W, H} (HOST memory) of uint8 NHWC [N, Hi, Wi, 3]
+ *   (is_f32 = 0, x = p / 255) or fp32 NCHW [N, 3, Hi, Wi] (is_f32 = 1).  resize != 0: Ho = Wo = 299, F.upsample(x, (299, 299), mode='bilinear') =
+ *   align_corners False, no antialias, for enlarging and reducing alike; resize = 0: Ho = H, Wo = W.  normalize != 0: x[c] s_c / 0.5 + (m_c - 0.5) /
+ *   0.5 with s = (0.229, 0.224, 0.225), m = (0.485, 0.456, 0.406) -- the reference applies this remap, which torchvision means for [-1, 1] inputs, to
+ *   [0, 1] images; kept, not corrected.  Coordinates are exact rationals and the arithmetic is fp64, rounded to fp32 once.
+ * pcdm_inception_features: out (fp32 [N, dims], device) = the global spatial mean of the block output with dims channels, dims in {64, 192, 768,
+ *   2048} = the reference's BLOCK_INDEX_BY_DIM (64: first max-pool, 192: second max-pool, 768: Mixed_6e, 2048: Mixed_7c = pool3).  Image arguments
+ *   as pcdm_inception_input.  Every convolution is Conv2d(bias = False) + BatchNorm2d(eps = 1e-3, running statistics) + ReLU; the caller folds the
+ *   BatchNorm into weight and bias (fp64, rounded to fp32 once) and packs with pcdm_pack_lpips_conv.  The 94 convolutions, in the order of
+ *   pcdm_inception_weights (= torchvision's module order):
+ *     0-4   Conv2d_1a_3x3, Conv2d_2a_3x3, Conv2d_2b_3x3, Conv2d_3b_1x1, Conv2d_4a_3x3 (a 3 x 3 / stride-2 max-pool after 2b and after 4a)
+ *     5-25  Mixed_5b, Mixed_5c, Mixed_5d (InceptionA), 7 each: branch1x1, branch5x5_1, branch5x5_2, branch3x3dbl_1, _2, _3, branch_pool
+ *     26-29 Mixed_6a (InceptionB): branch3x3, branch3x3dbl_1, _2, _3
+ *     30-69 Mixed_6b .. Mixed_6e (InceptionC), 10 each: branch1x1, branch7x7_1, _2, _3, branch7x7dbl_1, _2, _3, _4, _5, branch_pool
+ *     70-75 Mixed_7a (InceptionD): branch3x3_1, _2, branch7x7x3_1, _2, _3, _4
+ *     76-93 Mixed_7b, Mixed_7c (InceptionE), 9 each: branch1x1, branch3x3_1, _2a, _2b, branch3x3dbl_1, _2, _3a, _3b, branch_pool
+ *   dims = 64 / 192 / 768 / 2048 uses the first 3 / 5 / 70 / 94 of them; the others may be NULL.  The network input (299 x 299, or the window when
+ *   resize = 0) must leave every layer at least one output: 75 x 75 is the smallest for dims = 2048.  N <= 65535, N H W < 2^27.
+ *   ws: pcdm_inception_ws_bytes(N, H, W, dims) bytes for an H x W NETWORK input (299, 299 when resizing), 16-byte aligned, no initialisation.
+ *   No atomics, no allocation, no host synchronisation; reruns are bit-identical and a row's features do not depend on its place in the batch.
+ *   Returns -1 and writes nothing for any argument outside the above.
+ * pcdm_fid_accumulate: sum[j] += sum_b feat[b, j], gram[i, j] += sum_b feat[b, i] feat[b, j] for feat fp32 [B, D], sum fp64 [D], gram fp64 [D, D]
+ *   (zeroed by the caller before the first batch): one thread per output, the samples in order, products and sums in fp64 -- the state after n
+ *   samples is bit-identical however they were split into batches.  D <= 8192.
+ * pcdm_fid_finalize: mu = sum / n, sigma[i, j] = (gram[i, j] - sum[i] sum[j] / n) / (n - 1) = np.cov(rowvar = False), symmetric bit for bit; n >= 2. */
+typedef struct pcdm_inception_weights {
+    const float* w[94];      /* device, pcdm_pack_lpips_conv layout, BatchNorm folded in */
+    const float* bias[94];   /* device, fp32 [Npad] */
+} pcdm_inception_weights;
+int pcdm_conv2d_f32_ex(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw, int stride,
+                       int pad_h, int pad_w, int relu, float* out, int out_pitch, int out_offset, pcdm_stream_t s);
+int pcdm_maxpool3s2_f32_ex(const float* x, int B, int Hi, int Wi, int C, float* out, int out_pitch, int out_offset, pcdm_stream_t s);
+int pcdm_avgpool3_f32(const float* x, int B, int H, int W, int C, float* out, pcdm_stream_t s);
+int pcdm_global_avgpool_f32(const float* x, int B, int P, int C, float* out, pcdm_stream_t s);
+int pcdm_inception_input(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, float* out, pcdm_stream_t s);
+int64_t pcdm_inception_ws_bytes(int B, int H, int W, int dims);
+int pcdm_inception_features(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, int dims,
+                            const pcdm_inception_weights* wts, float* out, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int pcdm_fid_accumulate(const float* feat, int B, int D, double* sum, double* gram, pcdm_stream_t s);
+int pcdm_fid_finalize(const double* sum, const double* gram, int64_t n, int D, double* mu, double* sigma, pcdm_stream_t s);
+
 /* ---- Input preparation of the evaluation drivers (stage2_batchtest_inpaint_model.py:135-149: Image.resize((W, H), Image.BICUBIC), the
  * [source | black] and [source pose | target pose] canvases, ToTensor + Normalize, CLIPImageProcessor) on the device, from the decoded uint8 pixels.
  * pcdm_resample_u8: Pillow's 8-bit separable resampler.  src uint8 HWC [Hs, Ws, channels] (channels 3 or 1, contiguous) -> the Hd x Wd window at

@@ -76,6 +76,12 @@ class LpipsWeights(C.Structure):
     _fields_ = [("conv_w", C.c_void_p * 5), ("conv_b", C.c_void_p * 5), ("lin", C.c_void_p * 5)]
 
 
+class InceptionWeights(C.Structure):
+    """Mirror of ``pcdm_inception_weights`` (include/pcdm.h)."""
+
+    _fields_ = [("w", C.c_void_p * 94), ("bias", C.c_void_p * 94)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
 _SIGS = {
@@ -121,6 +127,15 @@ _SIGS = {
     "pcdm_maxpool3s2_f32": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "pcdm_lpips_ws_bytes": ([_I, _I, _I, _I], _L),
     "pcdm_lpips": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, C.POINTER(LpipsWeights), _P, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_conv2d_f32_ex": ([_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_maxpool3s2_f32_ex": ([_P, _I, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_avgpool3_f32": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_global_avgpool_f32": ([_P, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_inception_input": ([_P, _I, _I, _I, _W4, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_inception_ws_bytes": ([_I, _I, _I, _I], _L),
+    "pcdm_inception_features": ([_P, _I, _I, _I, _W4, _I, _I, _I, _I, C.POINTER(InceptionWeights), _P, _P, _L, _P], C.c_int),
+    "pcdm_fid_accumulate": ([_P, _I, _I, _P, _P, _P], C.c_int),
+    "pcdm_fid_finalize": ([_P, _P, _L, _I, _P, _P, _P], C.c_int),
     "pcdm_resample_ws_bytes": ([_I, _I, _I, _I, _I, _I], _L),
     "pcdm_resample_u8": ([_P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _L, _I, _I, _P, _L, _P], C.c_int),
     "pcdm_u8_to_nchw": ([_P, _I, _I, _I, _W4, _I, C.c_double, C.POINTER(_F), C.POINTER(_F), _P, _P], C.c_int),

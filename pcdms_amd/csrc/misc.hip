@@ -1133,8 +1133,8 @@ struct ConvF32 {
     const float* x;        // NHWC [B, Hi, Wi, Cin], Cin % 4 == 0
     const float* w;        // packed [Kpad / 4][Npad][4] (pcdm_pack_lpips_conv), k = (ky kw + kx) Cin + c
     const float* bias;     // [Npad]
-    float* out;            // NHWC [B, Ho, Wo, Cout]
-    int Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad, Kpad, M, relu;
+    float* out;            // channel 0 of the output slice: pixel m, channel n at out[m * ldo + n] (ldo = Cout: a tight NHWC [B, Ho, Wo, Cout])
+    int Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, Kpad, M, relu, ldo;
 };
 
 // One wave = a 32 x 64 output tile (2 x 4 accumulators of 16 x 16: eight independent MFMA chains), four waves along M per workgroup, operands
@@ -1159,8 +1159,8 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
         const int mm = valid[t] ? m : 0;
         const int b = mm / (p.Ho * p.Wo), q = mm - b * p.Ho * p.Wo;
         const int oy = q / p.Wo, ox = q - oy * p.Wo;
-        iy0[t] = oy * p.stride - p.pad;
-        ix0[t] = ox * p.stride - p.pad;
+        iy0[t] = oy * p.stride - p.pad_h;
+        ix0[t] = ox * p.stride - p.pad_w;
         xb[t] = p.x + (int64_t)b * p.Hi * p.Wi * p.Cin;
     }
     f32x4 acc[2][4];
@@ -1210,18 +1210,20 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
                 if (m >= p.M) continue;
                 float v = acc[t][j][e] + bv;
                 if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                p.out[(int64_t)m * p.Cout + n] = v;
+                p.out[(int64_t)m * p.ldo + n] = v;
             }
     }
 }
 
 // MaxPool2d(3, stride 2), no padding, floor: every window lies inside the image.  NHWC fp32, four channels per lane.
+// Pixel i / C4 of the output lies at out + (i / C4) * ldo4 four-channel groups (ldo4 = C4: a tight tensor; else a channel slice of a wider one).
 __global__ __launch_bounds__(256) void maxpool3s2_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int Hi, int Wi, int Ho, int Wo, int C4,
-                                                             int64_t total) {
+                                                             int ldo4, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over (b, oy, ox, c / 4)
     if (i >= total) return;
     const int c4 = (int)(i % C4);
     int64_t t = i / C4;
+    const int64_t pix = t;
     const int ox = (int)(t % Wo);
     t /= Wo;
     const int oy = (int)(t % Ho), b = (int)(t / Ho);
@@ -1235,7 +1237,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_f32_kernel(const float* __rest
 #pragma unroll
             for (int e = 0; e < 4; ++e) m[e] = v[e] > m[e] || v[e] != v[e] ? v[e] : m[e];
         }
-    ((f32x4*)out)[i] = m;
+    ((f32x4*)out)[pix * ldo4 + c4] = m;
 }
 
 // One tap: part[n * kLpSlices + slice] = sum over the slice's pixels of sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, f0 = image n,
@@ -1331,26 +1333,30 @@ inline bool lpips_sizes_ok(int N, int ref_n, int H, int W) {
     return N > 0 && N <= 65535 && (ref_n == 1 || ref_n == N) && H > 0 && W > 0 && (int64_t)(N + ref_n) * H * W < (int64_t)1 << 28;
 }
 
+// The output is the channel slice [off, off + Cout) of an NHWC tensor with ldo channels per pixel (ldo = Cout, off = 0: a tight tensor).
 inline int conv_f32_launch(const float* x, int B, int Hi, int Wi, int Cin, const float* w, const float* bias, int Cout, int kh, int kw, int stride,
-                           int pad, int relu, float* out, hipStream_t s) {
-    if (!x || !w || !bias || !out || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 4 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return -1;
+                           int pad_h, int pad_w, int relu, float* out, int ldo, int off, hipStream_t s) {
+    if (!x || !w || !bias || !out || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 4 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_h < 0 ||
+        pad_w < 0 || off < 0 || ldo < Cout || off > ldo - Cout)
+        return -1;
     if (((uintptr_t)x | (uintptr_t)w) & 15) return -1;
-    const int Ho = (Hi + 2 * pad - kh) / stride + 1, Wo = (Wi + 2 * pad - kw) / stride + 1;
-    if (Hi + 2 * pad < kh || Wi + 2 * pad < kw) return -1;
+    if (Hi + 2 * (int64_t)pad_h < kh || Wi + 2 * (int64_t)pad_w < kw || pad_h >= 1 << 20 || pad_w >= 1 << 20) return -1;
+    const int Ho = (Hi + 2 * pad_h - kh) / stride + 1, Wo = (Wi + 2 * pad_w - kw) / stride + 1;
     const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
     const int Npad = (Cout + 15) / 16 * 16;
-    if (M * Cout >= (int64_t)1 << 31 || (int64_t)B * Hi * Wi * Cin >= (int64_t)1 << 31 || K >= 1 << 24 || (Npad + 63) / 64 > 65535) return -1;
-    ConvF32 p{x, w, bias, out, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad, (int)((K + 15) / 16 * 16), (int)M, relu};
+    if (M * ldo >= (int64_t)1 << 31 || (int64_t)B * Hi * Wi * Cin >= (int64_t)1 << 31 || K >= 1 << 24 || (Npad + 63) / 64 > 65535) return -1;
+    ConvF32 p{x, w, bias, out + off, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, (int)((K + 15) / 16 * 16), (int)M, relu, ldo};
     PCDM_LAUNCH(conv_f32_kernel, dim3((unsigned)((M + 127) / 128), (Npad + 63) / 64), dim3(256), 0, s, p);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
-inline int maxpool_f32_launch(const float* x, int B, int Hi, int Wi, int C, float* out, hipStream_t s) {
+inline int maxpool_f32_launch(const float* x, int B, int Hi, int Wi, int C, float* out, int ldo, int off, hipStream_t s) {
     if (!x || !out || B <= 0 || Hi < 3 || Wi < 3 || C <= 0 || C % 4 || (((uintptr_t)x | (uintptr_t)out) & 15)) return -1;
-    if ((int64_t)B * Hi * Wi * C >= (int64_t)1 << 31) return -1;
+    if (off < 0 || off % 4 || ldo % 4 || ldo < C || off > ldo - C) return -1;
     const int Ho = (Hi - 3) / 2 + 1, Wo = (Wi - 3) / 2 + 1;
+    if ((int64_t)B * Hi * Wi * C >= (int64_t)1 << 31 || (int64_t)B * Ho * Wo * ldo >= (int64_t)1 << 31) return -1;
     const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
-    PCDM_LAUNCH(maxpool3s2_f32_kernel, grid1d(total, 256), dim3(256), 0, s, x, out, Hi, Wi, Ho, Wo, C / 4, total);
+    PCDM_LAUNCH(maxpool3s2_f32_kernel, grid1d(total, 256), dim3(256), 0, s, x, out + off, Hi, Wi, Ho, Wo, C / 4, ldo / 4, total);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -1381,11 +1387,11 @@ extern "C" int pcdm_pack_lpips_conv(const float* w, const float* bias, int Cout,
 
 extern "C" int pcdm_conv2d_f32(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw,
                                int stride, int pad, int relu, float* out, pcdm_stream_t s) {
-    return conv_f32_launch(x, B, Hi, Wi, Cin, w_packed, bias, Cout, kh, kw, stride, pad, relu, out, (hipStream_t)s);
+    return conv_f32_launch(x, B, Hi, Wi, Cin, w_packed, bias, Cout, kh, kw, stride, pad, pad, relu, out, Cout, 0, (hipStream_t)s);
 }
 
 extern "C" int pcdm_maxpool3s2_f32(const float* x, int B, int Hi, int Wi, int C, float* out, pcdm_stream_t s) {
-    return maxpool_f32_launch(x, B, Hi, Wi, C, out, (hipStream_t)s);
+    return maxpool_f32_launch(x, B, Hi, Wi, C, out, C, 0, (hipStream_t)s);
 }
 
 extern "C" int64_t pcdm_lpips_ws_bytes(int N, int ref_n, int H, int W) {
@@ -1418,13 +1424,13 @@ extern "C" int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t
     PCDM_LAUNCH(lpips_input_kernel, grid1d(total, 256), dim3(256), 0, st, LpSrc{img0, H0, W0, win0[0], win0[1]}, LpSrc{img1, H1, W1, win1[0], win1[1]}, N,
                 is_f32, normalize, W, H, total, x);
     PCDM_CHECK_LAUNCH();
-    int rc = conv_f32_launch(x, B, H, W, 4, wts->conv_w[0], wts->conv_b[0], 64, 11, 11, 4, 2, 1, tap[0], st);
-    if (rc == 0) rc = maxpool_f32_launch(tap[0], B, g.h[0], g.w[0], 64, pool[0], st);
-    if (rc == 0) rc = conv_f32_launch(pool[0], B, g.hp[0], g.wp[0], 64, wts->conv_w[1], wts->conv_b[1], 192, 5, 5, 1, 2, 1, tap[1], st);
-    if (rc == 0) rc = maxpool_f32_launch(tap[1], B, g.h[1], g.w[1], 192, pool[1], st);
-    if (rc == 0) rc = conv_f32_launch(pool[1], B, g.hp[1], g.wp[1], 192, wts->conv_w[2], wts->conv_b[2], 384, 3, 3, 1, 1, 1, tap[2], st);
-    if (rc == 0) rc = conv_f32_launch(tap[2], B, g.h[2], g.w[2], 384, wts->conv_w[3], wts->conv_b[3], 256, 3, 3, 1, 1, 1, tap[3], st);
-    if (rc == 0) rc = conv_f32_launch(tap[3], B, g.h[3], g.w[3], 256, wts->conv_w[4], wts->conv_b[4], 256, 3, 3, 1, 1, 1, tap[4], st);
+    int rc = conv_f32_launch(x, B, H, W, 4, wts->conv_w[0], wts->conv_b[0], 64, 11, 11, 4, 2, 2, 1, tap[0], 64, 0, st);
+    if (rc == 0) rc = maxpool_f32_launch(tap[0], B, g.h[0], g.w[0], 64, pool[0], 64, 0, st);
+    if (rc == 0) rc = conv_f32_launch(pool[0], B, g.hp[0], g.wp[0], 64, wts->conv_w[1], wts->conv_b[1], 192, 5, 5, 1, 2, 2, 1, tap[1], 192, 0, st);
+    if (rc == 0) rc = maxpool_f32_launch(tap[1], B, g.h[1], g.w[1], 192, pool[1], 192, 0, st);
+    if (rc == 0) rc = conv_f32_launch(pool[1], B, g.hp[1], g.wp[1], 192, wts->conv_w[2], wts->conv_b[2], 384, 3, 3, 1, 1, 1, 1, tap[2], 384, 0, st);
+    if (rc == 0) rc = conv_f32_launch(tap[2], B, g.h[2], g.w[2], 384, wts->conv_w[3], wts->conv_b[3], 256, 3, 3, 1, 1, 1, 1, tap[3], 256, 0, st);
+    if (rc == 0) rc = conv_f32_launch(tap[3], B, g.h[3], g.w[3], 256, wts->conv_w[4], wts->conv_b[4], 256, 3, 3, 1, 1, 1, 1, tap[4], 256, 0, st);
     if (rc != 0) return rc;
     LpCounts cnt;
     for (int l = 0; l < 5; ++l) {
@@ -1434,6 +1440,375 @@ extern "C" int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t
         PCDM_CHECK_LAUNCH();
     }
     PCDM_LAUNCH(lpips_final_kernel, dim3(1), dim3(256), 0, st, part, N, cnt, out, layers, argmin);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_conv2d_f32_ex(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw,
+                                  int stride, int pad_h, int pad_w, int relu, float* out, int out_pitch, int out_offset, pcdm_stream_t s) {
+    return conv_f32_launch(x, B, Hi, Wi, Cin, w_packed, bias, Cout, kh, kw, stride, pad_h, pad_w, relu, out, out_pitch, out_offset, (hipStream_t)s);
+}
+
+extern "C" int pcdm_maxpool3s2_f32_ex(const float* x, int B, int Hi, int Wi, int C, float* out, int out_pitch, int out_offset, pcdm_stream_t s) {
+    return maxpool_f32_launch(x, B, Hi, Wi, C, out, out_pitch, out_offset, (hipStream_t)s);
+}
+
+// ---- FID (the paper's third metric; the reference's metrics.py:23-257 + inception.py): torchvision's InceptionV3 trunk in exact fp32 -----------------
+// input stage (bilinear 299 x 299 resample + the reference's remap) -> 94 x [convolution, BatchNorm folded on the host, ReLU] on conv_f32_kernel,
+// every branch writing its channel slice of the block's concatenated tensor -> global average pool -> fp64 sum / Gram accumulation over the
+// samples -> mean and covariance.  Like LPIPS: NHWC fp32 activations, no atomics, fixed summation orders, no allocation, no host synchronisation.
+namespace {
+// out fp32 NHWC [N, Ho, Wo, 4] (channel 3 = 0) <- the window (x0, y0, Ws, Hs) of uint8 NHWC [N, Hi, Wi, 3] (x = p / 255) or fp32 NCHW [N, 3, Hi, Wi].
+// resize: bilinear, align_corners = False, no antialias (F.interpolate): source coordinate (o + 0.5) Ws / Wo - 0.5 clamped at 0, as the exact
+// rational ((2 o + 1) Ws - Wo) / (2 Wo); the neighbour index is clamped at the window's last pixel.  normalize: the reference's remap
+// x s_c / 0.5 + (m_c - 0.5) / 0.5.  Everything in fp64, rounded to fp32 once.
+__global__ __launch_bounds__(256) void inception_input_kernel(LpSrc s, int Hs, int Ws, int f32, int resize, int normalize, int Ho, int Wo, int64_t total,
+                                                              float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over (image, y, x)
+    if (i >= total) return;
+    const int x = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int y = (int)(t % Ho), n = (int)(t / Ho);
+    int xa = x, xb = x, ya = y, yb = y;
+    double lx = 0.0, ly = 0.0;
+    if (resize) {
+        const int64_t nx = (int64_t)(2 * x + 1) * Ws - Wo, ny = (int64_t)(2 * y + 1) * Hs - Ho;
+        if (nx > 0) { xa = (int)(nx / (2 * Wo)); lx = (double)(nx % (2 * Wo)) / (double)(2 * Wo); } else xa = 0;
+        if (ny > 0) { ya = (int)(ny / (2 * Ho)); ly = (double)(ny % (2 * Ho)) / (double)(2 * Ho); } else ya = 0;
+        xa = imin(xa, Ws - 1);
+        ya = imin(ya, Hs - 1);
+        xb = imin(xa + 1, Ws - 1);
+        yb = imin(ya + 1, Hs - 1);
+    }
+    const int64_t plane = (int64_t)s.Hi * s.Wi;
+    const int64_t p00 = (int64_t)(s.y0 + ya) * s.Wi + s.x0 + xa, p01 = (int64_t)(s.y0 + ya) * s.Wi + s.x0 + xb;
+    const int64_t p10 = (int64_t)(s.y0 + yb) * s.Wi + s.x0 + xa, p11 = (int64_t)(s.y0 + yb) * s.Wi + s.x0 + xb;
+    const double sc[3] = {0.229 / 0.5, 0.224 / 0.5, 0.225 / 0.5}, sh[3] = {(0.485 - 0.5) / 0.5, (0.456 - 0.5) / 0.5, (0.406 - 0.5) / 0.5};
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double v00, v01, v10, v11;
+        if (f32) {
+            const float* q = (const float*)s.p + ((int64_t)n * 3 + c) * plane;
+            v00 = q[p00]; v01 = q[p01]; v10 = q[p10]; v11 = q[p11];
+        } else {
+            const uint8_t* q = (const uint8_t*)s.p + (int64_t)n * plane * 3 + c;
+            v00 = q[p00 * 3] / 255.0; v01 = q[p01 * 3] / 255.0; v10 = q[p10 * 3] / 255.0; v11 = q[p11 * 3] / 255.0;
+        }
+        double v = (1.0 - ly) * ((1.0 - lx) * v00 + lx * v01) + ly * ((1.0 - lx) * v10 + lx * v11);
+        if (normalize) v = v * sc[c] + sh[c];
+        o[c] = (float)v;
+    }
+    *(f32x4*)(out + i * 4) = o;
+}
+
+// F.avg_pool2d(x, 3, 1, 1), count_include_pad: the nine taps in (dy, dx) order in fp32, zeros outside, divided by 9.  NHWC, four channels per lane.
+__global__ __launch_bounds__(256) void avgpool3_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W, int C4, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over (b, y, x, c / 4)
+    if (i >= total) return;
+    const int c4 = (int)(i % C4);
+    int64_t t = i / C4;
+    const int px = (int)(t % W);
+    t /= W;
+    const int py = (int)(t % H), b = (int)(t / H);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int yy = py + dy, xx = px + dx;
+            if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
+            const f32x4 v = ((const f32x4*)x)[(((int64_t)b * H + yy) * W + xx) * C4 + c4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] += v[e];
+        }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] /= 9.0f;
+    ((f32x4*)out)[i] = acc;
+}
+
+// out[b, c] = float(sum over the P pixels, in pixel order, in fp64 / P) of NHWC [B, P, C]: one lane per output, lanes along c
+__global__ __launch_bounds__(256) void global_avgpool_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int P, int C, int total) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = i % C, b = i / C;
+    const float* src = x + (int64_t)b * P * C + c;
+    double acc = 0.0;
+    for (int p = 0; p < P; ++p) acc += (double)src[(int64_t)p * C];
+    out[i] = (float)(acc / (double)P);
+}
+
+// One lane per output: gram[i, j] += sum_b x[b, i] x[b, j] (i * D + j < D D), sum[j] += sum_b x[b, j] (the D lanes after those), the samples in
+// order, in fp64 (the product of two fp32 values is exact there).  Adding a batch continues the chain the previous one left, so the state after
+// n samples does not depend on how they were split into batches.
+__global__ __launch_bounds__(256) void fid_accumulate_kernel(const float* __restrict__ x, int B, int D, double* __restrict__ sum, double* __restrict__ gram) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, DD = (int64_t)D * D;
+    if (t >= DD + D) return;
+    if (t < DD) {
+        const int i = (int)(t / D), j = (int)(t % D);
+        double acc = gram[t];
+        for (int b = 0; b < B; ++b) acc += (double)x[(int64_t)b * D + i] * (double)x[(int64_t)b * D + j];
+        gram[t] = acc;
+    } else {
+        const int j = (int)(t - DD);
+        double acc = sum[j];
+        for (int b = 0; b < B; ++b) acc += (double)x[(int64_t)b * D + j];
+        sum[j] = acc;
+    }
+}
+
+// mu = sum / n; sigma[i, j] = (gram[i, j] - sum[i] sum[j] / n) / (n - 1): np.cov(rowvar=False) (ddof 1), symmetric bit for bit
+__global__ __launch_bounds__(256) void fid_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ gram, double n, int D,
+                                                           double* __restrict__ mu, double* __restrict__ sigma) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, DD = (int64_t)D * D;
+    if (t >= DD + D) return;
+    if (t < DD) {
+        const int i = (int)(t / D), j = (int)(t % D);
+        sigma[t] = (gram[t] - sum[i] * sum[j] / n) / (n - 1.0);
+    } else {
+        mu[t - DD] = sum[t - DD] / n;
+    }
+}
+
+inline int avgpool3_f32_launch(const float* x, int B, int H, int W, int C, float* out, hipStream_t s) {
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || (((uintptr_t)x | (uintptr_t)out) & 15)) return -1;
+    if ((int64_t)B * H * W * C >= (int64_t)1 << 31) return -1;
+    const int64_t total = (int64_t)B * H * W * (C / 4);
+    PCDM_LAUNCH(avgpool3_f32_kernel, grid1d(total, 256), dim3(256), 0, s, x, out, H, W, C / 4, total);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+inline int global_avgpool_f32_launch(const float* x, int B, int P, int C, float* out, hipStream_t s) {
+    if (!x || !out || B <= 0 || P <= 0 || C <= 0 || (int64_t)B * P * C >= (int64_t)1 << 31) return -1;
+    PCDM_LAUNCH(global_avgpool_f32_kernel, grid1d((int64_t)B * C, 256), dim3(256), 0, s, x, out, P, C, B * C);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+inline int inception_input_launch(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, float* out,
+                                  hipStream_t s) {
+    if (!img || !out || N <= 0 || !met_window_ok(Hi, Wi, win) || ((uintptr_t)out & 15)) return -1;
+    const int Ho = resize ? 299 : win[3], Wo = resize ? 299 : win[2];
+    if ((int64_t)N * Hi * Wi * 3 >= (int64_t)1 << 31 || (int64_t)N * Ho * Wo * 4 >= (int64_t)1 << 31) return -1;
+    const int64_t total = (int64_t)N * Ho * Wo;
+    PCDM_LAUNCH(inception_input_kernel, grid1d(total, 256), dim3(256), 0, s, LpSrc{img, Hi, Wi, win[0], win[1]}, win[3], win[2], is_f32, resize, normalize,
+                Ho, Wo, total, out);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the trunk as a table.  Buffers: X = the input stage's output, A / B = a block's input and output (they swap), T / U = a branch's intermediates,
+// P = the 3 x 3 average of the block input.  The convolutions are numbered in the order they are appended = include/pcdm.h's order.
+enum { kIncX = 0, kIncA, kIncB, kIncT, kIncU, kIncP, kIncBufs };
+enum { kIncConv = 0, kIncMax, kIncAvg };
+constexpr int kIncConvs = 94, kIncMaxOps = 128;
+struct IncOp { int kind, src, dst, Hi, Wi, Cin, Cout, kh, kw, stride, ph, pw, ldo, off, conv; };
+struct IncPlan {
+    IncOp op[kIncMaxOps];
+    int n = 0, convs = 0, H = 0, W = 0, C = 0, buf = kIncX;   // the running tensor
+    int64_t elems[kIncBufs] = {0, 0, 0, 0, 0, 0};             // per image
+    bool ok = true;
+    void use(int buf_, int64_t e) { if (e > elems[buf_]) elems[buf_] = e; }
+    // a convolution src [Hi, Wi, Cin] -> channels [off, off + Cout) of dst [Ho, Wo, ldo]; returns through ho / wo
+    void conv(int src, int Hi, int Wi, int Cin, int dst, int Cout, int kh, int kw, int stride, int ph, int pw, int ldo, int off, int* ho, int* wo) {
+        if (Hi + 2 * ph < kh || Wi + 2 * pw < kw || n >= kIncMaxOps) { ok = false; *ho = *wo = 1; return; }
+        *ho = (Hi + 2 * ph - kh) / stride + 1;
+        *wo = (Wi + 2 * pw - kw) / stride + 1;
+        op[n++] = IncOp{kIncConv, src, dst, Hi, Wi, Cin, Cout, kh, kw, stride, ph, pw, ldo, off, convs++};
+        use(dst, (int64_t)*ho * *wo * ldo);
+    }
+    void pool(int kind, int src, int Hi, int Wi, int Cc, int dst, int ldo, int off, int* ho, int* wo) {
+        if ((kind == kIncMax && (Hi < 3 || Wi < 3)) || n >= kIncMaxOps) { ok = false; *ho = *wo = 1; return; }
+        *ho = kind == kIncMax ? (Hi - 3) / 2 + 1 : Hi;
+        *wo = kind == kIncMax ? (Wi - 3) / 2 + 1 : Wi;
+        op[n++] = IncOp{kind, src, dst, Hi, Wi, Cc, Cc, 3, 3, kind == kIncMax ? 2 : 1, 0, 0, ldo, off, -1};
+        use(dst, (int64_t)*ho * *wo * ldo);
+    }
+    // same-size helpers on the running tensor (stride 1, "same" padding): the branches of a Mixed block
+    void same(int src, int Cin, int dst, int Cout, int kh, int kw, int ldo, int off) {
+        int ho, wo;
+        conv(src, H, W, Cin, dst, Cout, kh, kw, 1, kh / 2, kw / 2, ldo, off, &ho, &wo);
+    }
+    int other() const { return buf == kIncA ? kIncB : kIncA; }
+    void done(int Cout, int ho, int wo) { buf = other(); C = Cout; H = ho; W = wo; }
+    void stem(int Cout, int k, int stride, int pad) {
+        int ho, wo;
+        conv(buf, H, W, C, other(), Cout, k, k, stride, pad, pad, Cout, 0, &ho, &wo);
+        done(Cout, ho, wo);
+    }
+    void stem_pool() {
+        int ho, wo;
+        pool(kIncMax, buf, H, W, C, other(), C, 0, &ho, &wo);
+        done(C, ho, wo);
+    }
+    void inception_a(int pf) {
+        const int in = buf, out = other(), ldo = 224 + pf;
+        same(in, C, out, 64, 1, 1, ldo, 0);
+        same(in, C, kIncT, 48, 1, 1, 48, 0);
+        same(kIncT, 48, out, 64, 5, 5, ldo, 64);
+        same(in, C, kIncT, 64, 1, 1, 64, 0);
+        same(kIncT, 64, kIncU, 96, 3, 3, 96, 0);
+        same(kIncU, 96, out, 96, 3, 3, ldo, 128);
+        int ho, wo;
+        pool(kIncAvg, in, H, W, C, kIncP, C, 0, &ho, &wo);
+        same(kIncP, C, out, pf, 1, 1, ldo, 224);
+        done(ldo, H, W);
+    }
+    void inception_b() {
+        const int in = buf, out = other(), ldo = 384 + 96 + C;
+        int ho, wo, h2, w2;
+        conv(in, H, W, C, out, 384, 3, 3, 2, 0, 0, ldo, 0, &ho, &wo);
+        same(in, C, kIncT, 64, 1, 1, 64, 0);
+        same(kIncT, 64, kIncU, 96, 3, 3, 96, 0);
+        conv(kIncU, H, W, 96, out, 96, 3, 3, 2, 0, 0, ldo, 384, &h2, &w2);
+        pool(kIncMax, in, H, W, C, out, ldo, 480, &h2, &w2);
+        done(ldo, ho, wo);
+    }
+    void inception_c(int c7) {
+        const int in = buf, out = other(), ldo = 768;
+        same(in, C, out, 192, 1, 1, ldo, 0);
+        same(in, C, kIncT, c7, 1, 1, c7, 0);
+        same(kIncT, c7, kIncU, c7, 1, 7, c7, 0);
+        same(kIncU, c7, out, 192, 7, 1, ldo, 192);
+        same(in, C, kIncT, c7, 1, 1, c7, 0);
+        same(kIncT, c7, kIncU, c7, 7, 1, c7, 0);
+        same(kIncU, c7, kIncT, c7, 1, 7, c7, 0);
+        same(kIncT, c7, kIncU, c7, 7, 1, c7, 0);
+        same(kIncU, c7, out, 192, 1, 7, ldo, 384);
+        int ho, wo;
+        pool(kIncAvg, in, H, W, C, kIncP, C, 0, &ho, &wo);
+        same(kIncP, C, out, 192, 1, 1, ldo, 576);
+        done(ldo, H, W);
+    }
+    void inception_d() {
+        const int in = buf, out = other(), ldo = 320 + 192 + C;
+        int ho, wo, h2, w2;
+        same(in, C, kIncT, 192, 1, 1, 192, 0);
+        conv(kIncT, H, W, 192, out, 320, 3, 3, 2, 0, 0, ldo, 0, &ho, &wo);
+        same(in, C, kIncT, 192, 1, 1, 192, 0);
+        same(kIncT, 192, kIncU, 192, 1, 7, 192, 0);
+        same(kIncU, 192, kIncT, 192, 7, 1, 192, 0);
+        conv(kIncT, H, W, 192, out, 192, 3, 3, 2, 0, 0, ldo, 320, &h2, &w2);
+        pool(kIncMax, in, H, W, C, out, ldo, 512, &h2, &w2);
+        done(ldo, ho, wo);
+    }
+    void inception_e() {
+        const int in = buf, out = other(), ldo = 2048;
+        same(in, C, out, 320, 1, 1, ldo, 0);
+        same(in, C, kIncT, 384, 1, 1, 384, 0);
+        same(kIncT, 384, out, 384, 1, 3, ldo, 320);
+        same(kIncT, 384, out, 384, 3, 1, ldo, 704);
+        same(in, C, kIncT, 448, 1, 1, 448, 0);
+        same(kIncT, 448, kIncU, 384, 3, 3, 384, 0);
+        same(kIncU, 384, out, 384, 1, 3, ldo, 1088);
+        same(kIncU, 384, out, 384, 3, 1, ldo, 1472);
+        int ho, wo;
+        pool(kIncAvg, in, H, W, C, kIncP, C, 0, &ho, &wo);
+        same(kIncP, C, out, 192, 1, 1, ldo, 1856);
+        done(ldo, H, W);
+    }
+};
+
+// the trunk up to the block whose output has `dims` channels, on an H x W network input; false: dims or a size the trunk cannot take
+inline bool inception_plan(int H, int W, int dims, IncPlan* p) {
+    if (dims != 64 && dims != 192 && dims != 768 && dims != 2048) return false;
+    if (H < 3 || W < 3 || H > 4096 || W > 4096) return false;
+    p->H = H; p->W = W; p->C = 4; p->buf = kIncX;
+    p->use(kIncX, (int64_t)H * W * 4);
+    p->stem(32, 3, 2, 0);                      // Conv2d_1a_3x3   (X -> A; from here A <-> B)
+    p->stem(32, 3, 1, 0);                      // Conv2d_2a_3x3
+    p->stem(64, 3, 1, 1);                      // Conv2d_2b_3x3
+    p->stem_pool();
+    if (dims > 64) {
+        p->stem(80, 1, 1, 0);                  // Conv2d_3b_1x1
+        p->stem(192, 3, 1, 0);                 // Conv2d_4a_3x3
+        p->stem_pool();
+    }
+    if (dims > 192) {
+        p->inception_a(32);                    // Mixed_5b, 5c, 5d
+        p->inception_a(64);
+        p->inception_a(64);
+        p->inception_b();                      // Mixed_6a
+        p->inception_c(128);                   // Mixed_6b .. 6e
+        p->inception_c(160);
+        p->inception_c(160);
+        p->inception_c(192);
+    }
+    if (dims > 768) {
+        p->inception_d();                      // Mixed_7a
+        p->inception_e();                      // Mixed_7b, 7c
+        p->inception_e();
+    }
+    return p->ok && p->C == dims;
+}
+inline bool inception_sizes_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (int64_t)1 << 27; }
+// workspace: the six buffers in enum order, each a multiple of 256 bytes; offsets in bytes
+struct IncLayout { int64_t at[kIncBufs], total; };
+inline IncLayout inception_layout(int B, const IncPlan& p) {
+    IncLayout o;
+    int64_t at = 0;
+    for (int i = 0; i < kIncBufs; ++i) { o.at[i] = at; at += lp_align((int64_t)B * p.elems[i] * (int64_t)sizeof(float)); }
+    o.total = at;
+    return o;
+}
+}  // namespace
+
+extern "C" int pcdm_avgpool3_f32(const float* x, int B, int H, int W, int C, float* out, pcdm_stream_t s) {
+    return avgpool3_f32_launch(x, B, H, W, C, out, (hipStream_t)s);
+}
+
+extern "C" int pcdm_global_avgpool_f32(const float* x, int B, int P, int C, float* out, pcdm_stream_t s) {
+    return global_avgpool_f32_launch(x, B, P, C, out, (hipStream_t)s);
+}
+
+extern "C" int pcdm_inception_input(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, float* out,
+                                    pcdm_stream_t s) {
+    return inception_input_launch(img, N, Hi, Wi, win, is_f32, resize, normalize, out, (hipStream_t)s);
+}
+
+extern "C" int64_t pcdm_inception_ws_bytes(int B, int H, int W, int dims) {
+    IncPlan p;
+    if (!inception_sizes_ok(B, H, W) || !inception_plan(H, W, dims, &p)) return -1;
+    return inception_layout(B, p).total;
+}
+
+extern "C" int pcdm_inception_features(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, int dims,
+                                       const pcdm_inception_weights* wts, float* out, void* ws, int64_t ws_bytes, pcdm_stream_t s) {
+    if (!img || !wts || !out || !ws || ((uintptr_t)ws & 15) || !met_window_ok(Hi, Wi, win)) return -1;
+    const int H = resize ? 299 : win[3], W = resize ? 299 : win[2];
+    IncPlan p;
+    if (!inception_sizes_ok(N, H, W) || !inception_plan(H, W, dims, &p)) return -1;
+    for (int i = 0; i < p.convs; ++i)
+        if (!wts->w[i] || !wts->bias[i]) return -1;
+    const IncLayout lay = inception_layout(N, p);
+    if (ws_bytes < lay.total) return -1;
+    float* buf[kIncBufs];
+    for (int i = 0; i < kIncBufs; ++i) buf[i] = (float*)((char*)ws + lay.at[i]);
+    hipStream_t st = (hipStream_t)s;
+    int rc = inception_input_launch(img, N, Hi, Wi, win, is_f32, resize, normalize, buf[kIncX], st);
+    for (int i = 0; i < p.n && rc == 0; ++i) {
+        const IncOp& o = p.op[i];
+        if (o.kind == kIncConv)
+            rc = conv_f32_launch(buf[o.src], N, o.Hi, o.Wi, o.Cin, wts->w[o.conv], wts->bias[o.conv], o.Cout, o.kh, o.kw, o.stride, o.ph, o.pw, 1, buf[o.dst],
+                                 o.ldo, o.off, st);
+        else if (o.kind == kIncMax)
+            rc = maxpool_f32_launch(buf[o.src], N, o.Hi, o.Wi, o.Cin, buf[o.dst], o.ldo, o.off, st);
+        else
+            rc = avgpool3_f32_launch(buf[o.src], N, o.Hi, o.Wi, o.Cin, buf[o.dst], st);
+    }
+    if (rc == 0) rc = global_avgpool_f32_launch(buf[p.buf], N, p.H * p.W, p.C, out, st);
+    return rc;
+}
+
+extern "C" int pcdm_fid_accumulate(const float* feat, int B, int D, double* sum, double* gram, pcdm_stream_t s) {
+    if (!feat || !sum || !gram || B <= 0 || D <= 0 || D > 8192 || (int64_t)B * D >= (int64_t)1 << 31) return -1;
+    PCDM_LAUNCH(fid_accumulate_kernel, grid1d((int64_t)D * D + D, 256), dim3(256), 0, (hipStream_t)s, feat, B, D, sum, gram);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_fid_finalize(const double* sum, const double* gram, int64_t n, int D, double* mu, double* sigma, pcdm_stream_t s) {
+    if (!sum || !gram || !mu || !sigma || n < 2 || D <= 0 || D > 8192) return -1;
+    PCDM_LAUNCH(fid_finalize_kernel, grid1d((int64_t)D * D + D, 256), dim3(256), 0, (hipStream_t)s, sum, gram, (double)n, D, mu, sigma);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

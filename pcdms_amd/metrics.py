@@ -14,6 +14,11 @@ Images are NHWC with 3 channels, uint8 or fp32 (candidates and reference the sam
 exact fp32 on the fp32-input MFMA (include/pcdm.h: pcdm_lpips).  Neither ``lpips`` nor ``torchvision`` is a dependency: the network is restated
 from its published definition and checked against an fp64 restatement with synthetic weights (tests/test_lpips.py), so parity with the upstream
 packages on their checkpoints is NOT pinned by a test here -- the same standing as the diffusers restatements.
+
+``InceptionV3Features`` / ``FIDStatistics`` / ``frechet_distance`` / ``FID`` are the third metric, the reference's FID (inception.py,
+metrics.py:23-257): the InceptionV3 trunk in exact fp32 and the fp64 statistics on the device (include/pcdm.h: pcdm_inception_features,
+pcdm_fid_accumulate, pcdm_fid_finalize), the Frechet distance itself on the host in fp64.  Same standing: restated, checked on synthetic weights
+(tests/test_fid.py), parity with torchvision's checkpoint not pinned.
 """
 from __future__ import annotations
 
@@ -214,3 +219,230 @@ class LPIPS:
         return (out, layers) if return_layers else out
 
     forward = __call__
+
+
+# ------------------------------------------------------------------------------------------------ FID
+def _inception_convs():
+    """(name, Cout, Cin, kh, kw) of the 94 BasicConv2d of torchvision's inception_v3 trunk in module order = pcdm_inception_weights' order."""
+    convs = [("Conv2d_1a_3x3", 32, 3, 3, 3), ("Conv2d_2a_3x3", 32, 32, 3, 3), ("Conv2d_2b_3x3", 64, 32, 3, 3), ("Conv2d_3b_1x1", 80, 64, 1, 1),
+             ("Conv2d_4a_3x3", 192, 80, 3, 3)]
+    for name, cin, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        convs += [(f"{name}.{b}", co, ci, kh, kw) for b, co, ci, kh, kw in (
+            ("branch1x1", 64, cin, 1, 1), ("branch5x5_1", 48, cin, 1, 1), ("branch5x5_2", 64, 48, 5, 5), ("branch3x3dbl_1", 64, cin, 1, 1),
+            ("branch3x3dbl_2", 96, 64, 3, 3), ("branch3x3dbl_3", 96, 96, 3, 3), ("branch_pool", pf, cin, 1, 1))]
+    convs += [(f"Mixed_6a.{b}", co, ci, 3 if b != "branch3x3dbl_1" else 1, 3 if b != "branch3x3dbl_1" else 1) for b, co, ci in (
+        ("branch3x3", 384, 288), ("branch3x3dbl_1", 64, 288), ("branch3x3dbl_2", 96, 64), ("branch3x3dbl_3", 96, 96))]
+    for name, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):
+        convs += [(f"{name}.{b}", co, ci, kh, kw) for b, co, ci, kh, kw in (
+            ("branch1x1", 192, 768, 1, 1), ("branch7x7_1", c7, 768, 1, 1), ("branch7x7_2", c7, c7, 1, 7), ("branch7x7_3", 192, c7, 7, 1),
+            ("branch7x7dbl_1", c7, 768, 1, 1), ("branch7x7dbl_2", c7, c7, 7, 1), ("branch7x7dbl_3", c7, c7, 1, 7), ("branch7x7dbl_4", c7, c7, 7, 1),
+            ("branch7x7dbl_5", 192, c7, 1, 7), ("branch_pool", 192, 768, 1, 1))]
+    convs += [(f"Mixed_7a.{b}", co, ci, kh, kw) for b, co, ci, kh, kw in (
+        ("branch3x3_1", 192, 768, 1, 1), ("branch3x3_2", 320, 192, 3, 3), ("branch7x7x3_1", 192, 768, 1, 1), ("branch7x7x3_2", 192, 192, 1, 7),
+        ("branch7x7x3_3", 192, 192, 7, 1), ("branch7x7x3_4", 192, 192, 3, 3))]
+    for name, cin in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        convs += [(f"{name}.{b}", co, ci, kh, kw) for b, co, ci, kh, kw in (
+            ("branch1x1", 320, cin, 1, 1), ("branch3x3_1", 384, cin, 1, 1), ("branch3x3_2a", 384, 384, 1, 3), ("branch3x3_2b", 384, 384, 3, 1),
+            ("branch3x3dbl_1", 448, cin, 1, 1), ("branch3x3dbl_2", 384, 448, 3, 3), ("branch3x3dbl_3a", 384, 384, 1, 3),
+            ("branch3x3dbl_3b", 384, 384, 3, 1), ("branch_pool", 192, cin, 1, 1))]
+    assert len(convs) == 94
+    return tuple(convs)
+
+
+INCEPTION_CONVS = _inception_convs()
+INCEPTION_CONVS_BY_DIM = {64: 3, 192: 5, 768: 70, 2048: 94}      # the reference's BLOCK_INDEX_BY_DIM: how many convolutions each output needs
+BN_EPS = 1e-3
+
+
+class InceptionV3Features:
+    """The feature extractor of the reference's FID (inception.py: ``InceptionV3([BLOCK_INDEX_BY_DIM[dims]])`` followed by the spatial mean that
+    metrics.py applies): torchvision's ``inception_v3`` trunk, eval mode, in exact fp32 on the device.  ``model(images)`` -> fp32 ``[N, dims]``.
+
+    Images are in [0, 1]: fp32 NCHW [N, 3, H, W] or uint8 NHWC [N, H, W, 3] (x = p / 255), optionally a ``window`` (x0, y0, W, H) of them, as
+    ``LPIPS`` takes them.  ``resize_input``: ``F.upsample(x, (299, 299), mode='bilinear')`` (align_corners False, no antialias);
+    ``False`` feeds the window at its own size (at least 75 x 75 for ``dims=2048``).  ``normalize_input``: the reference's remap
+    ``x[c] * (s_c / 0.5) + (m_c - 0.5) / 0.5``.  **Torchvision means that formula for [-1, 1] inputs; the reference feeds it [0, 1] images.**  The
+    quirk is reproduced, not corrected, as LPIPS's is.  Every BatchNorm (eps 1e-3, running statistics) is folded into its convolution's weight
+    and bias in fp64 and rounded to fp32 once.  ``torchvision`` is not a dependency; the trunk is checked against an fp64 restatement with
+    synthetic weights (tests/test_fid.py), so parity with torchvision on its checkpoint is NOT pinned here."""
+
+    def __init__(self, dims: int = 2048, resize_input: bool = True, normalize_input: bool = True):
+        if dims not in INCEPTION_CONVS_BY_DIM:
+            raise ValueError(f"dims must be one of {sorted(INCEPTION_CONVS_BY_DIM)} (the reference's BLOCK_INDEX_BY_DIM), not {dims!r}")
+        self.dims, self.resize_input, self.normalize_input = dims, bool(resize_input), bool(normalize_input)
+        self.packed: list = []                         # host: per convolution {"w", "bias"} in the library's layout
+        self._dev: Dict[str, tuple] = {}
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> "InceptionV3Features":
+        """torchvision's ``inception_v3`` layout: ``<layer>.conv.weight`` and ``<layer>.bn.{weight, bias, running_mean, running_var}`` for the
+        convolutions this ``dims`` needs; ``AuxLogits.*``, ``fc.*``, ``num_batches_tracked`` and later layers are ignored."""
+        packed = []
+        for name, cout, cin, kh, kw in INCEPTION_CONVS[:INCEPTION_CONVS_BY_DIM[self.dims]]:
+            keys = [f"{name}.conv.weight"] + [f"{name}.bn.{k}" for k in ("weight", "bias", "running_mean", "running_var")]
+            for k in keys:
+                if k not in sd:
+                    raise KeyError(f"{k} is missing (torchvision's inception_v3 layout)")
+            w, (g, b, m, v) = sd[keys[0]], (sd[k] for k in keys[1:])
+            if tuple(w.shape) != (cout, cin, kh, kw):
+                raise ValueError(f"{name}.conv.weight: shape {tuple(w.shape)}, InceptionV3 has {(cout, cin, kh, kw)}")
+            for k, t in zip(keys[1:], (g, b, m, v)):
+                if tuple(t.shape) != (cout,):
+                    raise ValueError(f"{k}: shape {tuple(t.shape)}, InceptionV3 has {(cout,)}")
+            g, b, m, v = (t.detach().to("cpu", torch.float64) for t in (g, b, m, v))
+            scale = g / torch.sqrt(v + BN_EPS)
+            wf = (w.detach().to("cpu", torch.float64) * scale.view(-1, 1, 1, 1)).to(torch.float32)
+            pw = ops.pack_lpips_conv(wf, (b - m * scale).to(torch.float32), "cpu")
+            packed.append({"w": pw["w"], "bias": pw["bias"]})
+        self.packed, self._dev = packed, {}
+        return self
+
+    @classmethod
+    def from_pretrained(cls, path, dims: int = 2048, resize_input: bool = True, normalize_input: bool = True) -> "InceptionV3Features":
+        """A ``.pth`` / ``.pt`` (torch.load) or ``.safetensors`` file of torchvision's ``inception_v3`` state dict."""
+        if str(path).endswith(".safetensors"):
+            from safetensors.torch import load_file
+            sd = load_file(str(path))
+        else:
+            sd = torch.load(str(path), map_location="cpu", weights_only=True)
+        return cls(dims, resize_input, normalize_input).load_state_dict(dict(sd))
+
+    def _weights(self, device: torch.device):
+        if not self.packed:
+            raise RuntimeError("InceptionV3Features has no weights: load_state_dict / from_pretrained first")
+        key = str(device)
+        if key not in self._dev:
+            t = [{k: v.to(device) for k, v in p.items()} for p in self.packed]
+            w = _lib.InceptionWeights()
+            for i, p in enumerate(t):
+                w.w[i], w.bias[i] = p["w"].data_ptr(), p["bias"].data_ptr()
+            self._dev[key] = (t, w)
+        return self._dev[key][1]
+
+    def __call__(self, images: torch.Tensor, window: Window = None) -> torch.Tensor:
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"images are fp32 [N, 3, H, W] or uint8 [N, H, W, 3]: got {getattr(images, 'dtype', type(images))} "
+                             f"{tuple(getattr(images, 'shape', ()))}")
+        f32 = images.dtype == torch.float32
+        H, W = (images.shape[2], images.shape[3]) if f32 else (images.shape[1], images.shape[2])
+        if images.shape[1 if f32 else 3] != 3:
+            raise ValueError(f"three channels expected: got {tuple(images.shape)}")
+        win = tuple(int(v) for v in window) if window is not None else (0, 0, W, H)
+        if len(win) != 4 or win[0] < 0 or win[1] < 0 or win[2] < 1 or win[3] < 1 or win[0] + win[2] > W or win[1] + win[3] > H:
+            raise ValueError(f"window {win} (x0, y0, W, H) does not lie inside the {W} x {H} image")
+        N, dev = images.shape[0], images.device
+        weights = self._weights(dev)
+        h, w = (299, 299) if self.resize_input else (win[3], win[2])
+        nbytes = ops.inception_ws_bytes(N, h, w, self.dims)
+        if nbytes < 0:
+            raise ValueError(f"InceptionV3 (dims={self.dims}) cannot take a batch of {N} inputs of {w} x {h} (W x H): without resize_input the full "
+                             "trunk needs at least 75 x 75 pixels")
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+        out = torch.empty((N, self.dims), dtype=torch.float32, device=dev)
+        return ops.inception_features(images.contiguous(), win, weights, out, ws, dims=self.dims, resize=self.resize_input,
+                                      normalize=self.normalize_input)
+
+    forward = __call__
+
+
+class FIDStatistics:
+    """Running fp64 sum and Gram matrix of feature rows on the device; ``finalize()`` -> ``(mu, sigma)`` = ``np.mean(act, 0)``,
+    ``np.cov(act, rowvar=False)`` in fp64.  One thread owns each entry and adds the samples in order, so the state is bit-identical however the
+    samples are split into batches.  ``save`` / ``load`` use the reference's ``.npz`` format (keys ``mu``, ``sigma``)."""
+
+    def __init__(self, dims: int):
+        self.dims, self.count = int(dims), 0
+        self.sum: Optional[torch.Tensor] = None
+        self.gram: Optional[torch.Tensor] = None
+        self._final: Optional[Tuple[torch.Tensor, torch.Tensor]] = None      # a loaded file: nothing to accumulate
+
+    def update(self, features: torch.Tensor) -> "FIDStatistics":
+        if self._final is not None:
+            raise RuntimeError("statistics loaded from a file cannot take more samples")
+        if features.dim() != 2 or features.shape[1] != self.dims or features.dtype != torch.float32:
+            raise ValueError(f"features are fp32 [N, {self.dims}]: got {features.dtype} {tuple(features.shape)}")
+        if self.sum is None:
+            self.sum = torch.zeros(self.dims, dtype=torch.float64, device=features.device)
+            self.gram = torch.zeros((self.dims, self.dims), dtype=torch.float64, device=features.device)
+        elif self.sum.device != features.device:
+            raise ValueError(f"features on {features.device}, statistics on {self.sum.device}")
+        if features.shape[0]:
+            ops.fid_accumulate(features.contiguous(), self.sum, self.gram)
+            self.count += features.shape[0]
+        return self
+
+    def finalize(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._final is not None:
+            return self._final
+        if self.count < 2:
+            raise ValueError(f"a covariance needs at least two samples: {self.count} accumulated")
+        return ops.fid_finalize(self.sum, self.gram, self.count)
+
+    def save(self, path) -> None:
+        import numpy as np
+        mu, sigma = self.finalize()
+        with open(path, "wb") as f:      # (a file object: np.savez would append ".npz" to a bare name)
+            np.savez(f, mu=mu.cpu().numpy(), sigma=sigma.cpu().numpy())
+
+    @classmethod
+    def load(cls, path) -> "FIDStatistics":
+        import numpy as np
+        with np.load(str(path)) as f:
+            mu, sigma = torch.from_numpy(np.asarray(f["mu"], dtype=np.float64)), torch.from_numpy(np.asarray(f["sigma"], dtype=np.float64))
+        if mu.dim() != 1 or tuple(sigma.shape) != (mu.shape[0], mu.shape[0]):
+            raise ValueError(f"{path}: mu {tuple(mu.shape)}, sigma {tuple(sigma.shape)}")
+        st = cls(mu.shape[0])
+        st._final = (mu, sigma)
+        return st
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
+    """d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2), on the host in fp64.  S1 S2 is similar to the symmetric positive semi-definite
+    S1^1/2 S2 S1^1/2, so tr sqrt(S1 S2) is the sum of the square roots of that matrix's eigenvalues (clamped at 0), from two
+    ``torch.linalg.eigh`` on the CPU.  This replaces the reference's ``scipy.linalg.sqrtm(S1 S2)`` with its "singular product" retry on
+    S + eps I and its discarded imaginary part: no scipy, no fallback, finite for rank-deficient covariances (fewer samples than features); the
+    two agree wherever ``sqrtm`` is finite."""
+    def t(a):
+        return (a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to("cpu", torch.float64)
+    mu1, sigma1, mu2, sigma2 = t(mu1).flatten(), t(sigma1), t(mu2).flatten(), t(sigma2)
+    D = mu1.shape[0]
+    if mu2.shape[0] != D or tuple(sigma1.shape) != (D, D) or tuple(sigma2.shape) != (D, D):
+        raise ValueError(f"mean and covariance shapes differ: {tuple(mu1.shape)} {tuple(sigma1.shape)} {tuple(mu2.shape)} {tuple(sigma2.shape)}")
+    w, v = torch.linalg.eigh((sigma1 + sigma1.T) / 2)
+    root1 = (v * w.clamp_min(0).sqrt()) @ v.T
+    m = root1 @ ((sigma2 + sigma2.T) / 2) @ root1
+    tr_sqrt = torch.linalg.eigvalsh((m + m.T) / 2).clamp_min(0).sqrt().sum()
+    diff = mu1 - mu2
+    return float(diff.dot(diff) + torch.trace(sigma1) + torch.trace(sigma2) - 2 * tr_sqrt)
+
+
+class FID:
+    """``FID(model)`` with ``model`` an ``InceptionV3Features``: ``statistics(batches)`` runs every image batch through the trunk and accumulates
+    on the device; ``fid(a, b)`` is the Frechet distance of two ``FIDStatistics`` (or ``(mu, sigma)`` pairs, or ``.npz`` paths).
+    ``drop_remainder=B`` reproduces the reference, which processes ``len(images) // B`` full batches of ``B`` = 128 and silently drops the rest
+    (metrics.py:170-198): only the first ``(n // B) * B`` images count."""
+
+    def __init__(self, model: InceptionV3Features):
+        self.model = model
+
+    def statistics(self, batches, *, drop_remainder: Optional[int] = None) -> FIDStatistics:
+        st = FIDStatistics(self.model.dims)
+        feats = [self.model(b) for b in batches]
+        if drop_remainder:
+            B, n = int(drop_remainder), sum(f.shape[0] for f in feats)
+            keep = n // B * B if n >= B else n        # (a set smaller than one batch: the reference shrinks the batch to the set)
+            feats = [torch.cat(feats)[:keep]] if feats else []
+        for f in feats:
+            st.update(f)
+        return st
+
+    @staticmethod
+    def _stats(s):
+        if isinstance(s, FIDStatistics):
+            return s.finalize()
+        if isinstance(s, (str, bytes)) or hasattr(s, "__fspath__"):
+            return FIDStatistics.load(s).finalize()
+        return s
+
+    def __call__(self, stats_a, stats_b) -> float:
+        (m1, s1), (m2, s2) = self._stats(stats_a), self._stats(stats_b)
+        return frechet_distance(m1, s1, m2, s2)

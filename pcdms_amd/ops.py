@@ -1033,6 +1033,110 @@ def lpips(img0: torch.Tensor, img1: torch.Tensor, win0: Sequence[int], win1: Seq
     return out
 
 
+# ------------------------------------------------------------------------------------ FID (pcdms_amd/metrics.py: InceptionV3Features, FIDStatistics)
+def conv2d_f32_ex(x: torch.Tensor, pw: dict, *, stride: int = 1, pad: Sequence[int] = (0, 0), relu: bool = False, out: Optional[torch.Tensor] = None,
+                  offset: int = 0) -> torch.Tensor:
+    """``conv2d_f32`` with ``pad = (pad_h, pad_w)`` and, with ``out`` NHWC fp32 [B, Ho, Wo, pitch], the result written into its channels
+    ``[offset, offset + Cout)`` and nothing else of it touched (include/pcdm.h: pcdm_conv2d_f32_ex)."""
+    _c(x, torch.float32)
+    B, Hi, Wi, Cin = (int(v) for v in x.shape)
+    assert Cin == pw["cin"], (Cin, pw["cin"])
+    ph, pwd = int(pad[0]), int(pad[1])
+    Ho, Wo = (Hi + 2 * ph - pw["kh"]) // stride + 1, (Wi + 2 * pwd - pw["kw"]) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"a {pw['kh']} x {pw['kw']} kernel does not fit a {Hi} x {Wi} image padded by {(ph, pwd)}")
+    if out is None:
+        out = torch.empty((B, Ho, Wo, pw["cout"]), dtype=torch.float32, device=x.device)
+    _c(out, torch.float32)
+    if out.dim() != 4 or tuple(out.shape[:3]) != (B, Ho, Wo) or out.device != x.device:
+        raise ValueError(f"out {tuple(out.shape)} on {out.device}: expected [{B}, {Ho}, {Wo}, pitch] on {x.device}")
+    _chk(_lib.lib().pcdm_conv2d_f32_ex(_ptr(x), B, Hi, Wi, Cin, _ptr(pw["w"]), _ptr(pw["bias"]), pw["cout"], pw["kh"], pw["kw"], int(stride), ph, pwd,
+                                       int(relu), _ptr(out), int(out.shape[3]), int(offset), _stream(x)), "pcdm_conv2d_f32_ex")
+    return out
+
+
+def maxpool3s2_f32_ex(x: torch.Tensor, out: torch.Tensor, offset: int = 0) -> torch.Tensor:
+    """MaxPool2d(3, stride 2) of NHWC fp32 ``x`` into the channels ``[offset, offset + C)`` of ``out`` [B, Ho, Wo, pitch]
+    (include/pcdm.h: pcdm_maxpool3s2_f32_ex)."""
+    _c(x, torch.float32); _c(out, torch.float32)
+    B, Hi, Wi, Cn = (int(v) for v in x.shape)
+    if Hi < 3 or Wi < 3 or tuple(out.shape[:3]) != (B, (Hi - 3) // 2 + 1, (Wi - 3) // 2 + 1) or out.device != x.device:
+        raise ValueError(f"x {tuple(x.shape)}, out {tuple(out.shape)}")
+    _chk(_lib.lib().pcdm_maxpool3s2_f32_ex(_ptr(x), B, Hi, Wi, Cn, _ptr(out), int(out.shape[3]), int(offset), _stream(x)), "pcdm_maxpool3s2_f32_ex")
+    return out
+
+
+def avgpool3_f32(x: torch.Tensor) -> torch.Tensor:
+    """F.avg_pool2d(x, 3, 1, 1) (count_include_pad) on NHWC fp32 (include/pcdm.h: pcdm_avgpool3_f32)."""
+    _c(x, torch.float32)
+    B, H, W, Cn = (int(v) for v in x.shape)
+    out = torch.empty_like(x)
+    _chk(_lib.lib().pcdm_avgpool3_f32(_ptr(x), B, H, W, Cn, _ptr(out), _stream(x)), "pcdm_avgpool3_f32")
+    return out
+
+
+def global_avgpool_f32(x: torch.Tensor) -> torch.Tensor:
+    """NHWC fp32 [B, H, W, C] -> fp32 [B, C]: the spatial mean, summed in fp64 in pixel order (include/pcdm.h: pcdm_global_avgpool_f32)."""
+    _c(x, torch.float32)
+    B, H, W, Cn = (int(v) for v in x.shape)
+    out = torch.empty((B, Cn), dtype=torch.float32, device=x.device)
+    _chk(_lib.lib().pcdm_global_avgpool_f32(_ptr(x), B, H * W, Cn, _ptr(out), _stream(x)), "pcdm_global_avgpool_f32")
+    return out
+
+
+def _image_batch(img: torch.Tensor):
+    assert img.dim() == 4 and img.dtype in (torch.uint8, torch.float32) and img.is_contiguous(), (img.shape, img.dtype)
+    f32 = int(img.dtype == torch.float32)
+    H, W = (img.shape[2:]) if f32 else (img.shape[1:3])
+    assert (img.shape[1] if f32 else img.shape[3]) == 3, img.shape
+    return f32, int(H), int(W)
+
+
+def inception_input(img: torch.Tensor, win: Sequence[int], *, resize: bool, normalize: bool) -> torch.Tensor:
+    """uint8 NHWC [N, Hi, Wi, 3] or fp32 NCHW [N, 3, Hi, Wi], window (x0, y0, W, H) -> fp32 NHWC [N, 299 | H, 299 | W, 4]: the bilinear resample and
+    the reference's remap (include/pcdm.h: pcdm_inception_input)."""
+    f32, H, W = _image_batch(img)
+    Ho, Wo = (299, 299) if resize else (int(win[3]), int(win[2]))
+    out = torch.empty((img.shape[0], Ho, Wo, 4), dtype=torch.float32, device=img.device)
+    _chk(_lib.lib().pcdm_inception_input(_ptr(img), img.shape[0], H, W, _win(win), f32, int(resize), int(normalize), _ptr(out), _stream(img)),
+         "pcdm_inception_input")
+    return out
+
+
+def inception_ws_bytes(B: int, H: int, W: int, dims: int) -> int:
+    """Workspace bytes of ``inception_features`` for an H x W network input; -1: the library refuses the problem."""
+    return int(_lib.lib().pcdm_inception_ws_bytes(int(B), int(H), int(W), int(dims)))
+
+
+def inception_features(img: torch.Tensor, win: Sequence[int], weights: "_lib.InceptionWeights", out: torch.Tensor, ws: torch.Tensor, *, dims: int,
+                       resize: bool, normalize: bool) -> torch.Tensor:
+    """The InceptionV3 trunk as one C call: out fp32 [N, dims] (include/pcdm.h: pcdm_inception_features)."""
+    f32, H, W = _image_batch(img)
+    _c(out, torch.float32)
+    assert out.device == img.device and ws.device == img.device
+    _chk(_lib.lib().pcdm_inception_features(_ptr(img), img.shape[0], H, W, _win(win), f32, int(resize), int(normalize), int(dims), C.byref(weights),
+                                            _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream(img)), "pcdm_inception_features")
+    return out
+
+
+def fid_accumulate(feat: torch.Tensor, total: torch.Tensor, gram: torch.Tensor) -> None:
+    """total fp64 [D] += sum_b feat[b], gram fp64 [D, D] += sum_b feat[b] feat[b]^T for feat fp32 [B, D] (include/pcdm.h: pcdm_fid_accumulate)."""
+    _c(feat, torch.float32); _c(total, torch.float64); _c(gram, torch.float64)
+    B, D = (int(v) for v in feat.shape)
+    assert tuple(total.shape) == (D,) and tuple(gram.shape) == (D, D) and total.device == feat.device and gram.device == feat.device
+    _chk(_lib.lib().pcdm_fid_accumulate(_ptr(feat), B, D, _ptr(total), _ptr(gram), _stream(feat)), "pcdm_fid_accumulate")
+
+
+def fid_finalize(total: torch.Tensor, gram: torch.Tensor, n: int):
+    """-> (mu fp64 [D], sigma fp64 [D, D]) on the device: the mean and the ddof-1 covariance of the n accumulated samples
+    (include/pcdm.h: pcdm_fid_finalize)."""
+    _c(total, torch.float64); _c(gram, torch.float64)
+    D = int(total.shape[0])
+    mu, sigma = torch.empty_like(total), torch.empty_like(gram)
+    _chk(_lib.lib().pcdm_fid_finalize(_ptr(total), _ptr(gram), int(n), D, _ptr(mu), _ptr(sigma), _stream(total)), "pcdm_fid_finalize")
+    return mu, sigma
+
+
 # ------------------------------------------------------------------------------------ input preparation (pcdms_amd/preprocess.py is the public surface)
 def resample_ws_bytes(Hs: int, Ws: int, Hd: int, Wd: int, channels: int, ky: int) -> int:
     """Workspace bytes of ``resample_u8`` (0: one launch, no workspace); -1: the library refuses the problem."""
