@@ -468,6 +468,42 @@ int pcdm_resample_u8(const void* src, int Hs, int Ws, int channels, const int32_
 int pcdm_u8_to_nchw(const void* src_u8, int Hs, int Ws, int channels, const int32_t* win, int mode, double scale, const float* mean, const float* std_,
                     float* out, pcdm_stream_t s);
 
+/* ---- The reference's metric scripts (caculate_metrics_256.py / _512.py -> metrics.py: calculate_from_disk) on the device: the OpenCV resize in
+ * front of every metric, L1 / MAE, and the uniform-window SSIM of the `ssim` array.  OpenCV and scikit-image are not dependencies: the algorithms
+ * are restated from their published definitions and checked against fp64 restatements (tests/test_eval_metrics.py); parity with the packages
+ * themselves is NOT pinned by a test here -- the same standing as LPIPS and FID.
+ * pcdm_resize_cubic_f32: cv2.resize(img.astype(np.float32), (Wd, Hd), interpolation=cv2.INTER_CUBIC) [/ divisor] -- resizeGeneric_ with
+ *   HResizeCubic / VResizeCubic and the float work type.  src HWC [Hs, Ws, 3], uint8 (src_is_f32 = 0; converted as astype does) or fp32; the result
+ *   is image `index` of the fp32 batch dst, NHWC [N, Hd, Wd, 3] (nchw = 0) or NCHW [N, 3, Hd, Wd] (nchw = 1); no other image of dst is written.
+ *   Per axis scale = 1.0 / ((double)n_out / (double)n_in); for output d: f = (float)((d + 0.5) * scale - 0.5) (fp64, rounded once), s = floor(f),
+ *   t = f - s in fp32; taps are the source indices s - 1 .. s + 2, each clamped into [0, n_in - 1]; coefficients in fp32 with A = -0.75f:
+ *   c0 = ((A (t + 1) - 5 A)(t + 1) + 8 A)(t + 1) - 4 A, c1 = ((A + 2) t - (A + 3)) t t + 1, c2 = c1 at 1 - t, c3 = 1 - c0 - c1 - c2.  The
+ *   horizontal pass first, S[-1] c0 + S[0] c1 + S[1] c2 + S[2] c3 in fp32 from left to right into an fp32 row, then the vertical pass over those
+ *   rows in the same way.  No antialiasing when reducing, no rounding, no clipping: the result overshoots below 0 and above 255.  Equal sizes
+ *   copy the image bit for bit (t = 0: coefficients 0, 1, 0, 0).  divisor > 0: every output is x / divisor as a true fp32 division (the
+ *   reference's / 255.0).  Contraction is OFF in this kernel: every multiply and add above is its own IEEE operation, no fused multiply-add
+ *   (the rest of the library is built with -ffp-contract=fast), as a plain C++ build of OpenCV's generic path computes; reruns are bit-identical.
+ *   One launch: a workgroup owns a 32 x 16 output tile and stages the horizontally filtered source rows it needs in LDS (24 KB).  No atomics, no
+ *   workspace, no host synchronisation; every index is clamped on the device.  Returns -1 and writes nothing for channels != 3, non-positive
+ *   sizes, index outside [0, N), dst (or an fp32 src) not 4-byte aligned, or an image of 2^31 elements or more.
+ * pcdm_absdiff: l1[n] = mean |a - b| (compare_l1), mae[n] = sum |a - b| / sum (a + b) (compare_mae) over the windows; images, windows, ref_n and
+ *   refusals as for pcdm_psnr; ws: pcdm_metrics_ws_bytes(N, ref_n, W, H, 0) bytes.  a - b and a + b are formed in fp32 per element (as numpy does
+ *   on float32 arrays) and summed in fp64 -- uint8 inputs in integers, exact -- in a fixed order; the quotient is taken in fp64 and rounded to
+ *   fp32 once.  A zero denominator gives what IEEE division gives (NaN or inf).  Either output may be NULL.  Two launches.
+ * pcdm_ssim_box: scores[n] = skimage.metrics.structural_similarity(ref, cand[n], win_size=w, data_range=R, channel_axis=2) with skimage's
+ *   defaults: five moments under a w x w mean filter, NP = w^2, covariances multiplied by NP / (NP - 1) (the sample covariance), C1 = (0.01 R)^2,
+ *   C2 = (0.03 R)^2, the map averaged over the interior [p, H - p) x [p, W - p), p = (w - 1) / 2, and the channels (no tap of an averaged pixel
+ *   leaves the window, so the filter's boundary mode never enters).  w odd, 3 <= w <= 51 (the reference: 51); R = data_range, or, for data_range
+ *   < 0, max - min of the candidate's window.  fp64 accumulation on values centred per image, as pcdm_ssim: |score - fp64| <= 1e-5.  Other
+ *   arguments and refusals as for pcdm_ssim, plus W < w or H < w; ws: pcdm_ssim_box_ws_bytes.  Three launches, no atomics. */
+int pcdm_resize_cubic_f32(const void* src, int src_is_f32, int Hs, int Ws, int channels, float* dst, int N, int Hd, int Wd, int index, int nchw,
+                          float divisor, pcdm_stream_t s);
+int pcdm_absdiff(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr, const int32_t* ref_win,
+                 int channels, int is_f32, float* l1, float* mae, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int64_t pcdm_ssim_box_ws_bytes(int N, int ref_n, int W, int H, int win_size);
+int pcdm_ssim_box(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr, const int32_t* ref_win,
+                  int channels, int is_f32, int win_size, float data_range, float* scores, void* ws, int64_t ws_bytes, pcdm_stream_t s);
+
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host
  * that is not Python: pcdm_unet_create from the topology, pcdm_unet_set_weight / _set_vector with the packed tensors under their

@@ -139,6 +139,10 @@ _SIGS = {
     "pcdm_resample_ws_bytes": ([_I, _I, _I, _I, _I, _I], _L),
     "pcdm_resample_u8": ([_P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _L, _I, _I, _P, _L, _P], C.c_int),
     "pcdm_u8_to_nchw": ([_P, _I, _I, _I, _W4, _I, C.c_double, C.POINTER(_F), C.POINTER(_F), _P, _P], C.c_int),
+    "pcdm_resize_cubic_f32": ([_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P], C.c_int),
+    "pcdm_absdiff": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_ssim_box_ws_bytes": ([_I, _I, _I, _I, _I], _L),
+    "pcdm_ssim_box": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _I, _F, _P, _P, _L, _P], C.c_int),
     "pcdm_unet_create":([C.POINTER(UNetConfig)], _P),
     "pcdm_unet_destroy": ([_P], None),
     "pcdm_unet_last_error": ([_P], C.c_char_p),

@@ -749,6 +749,238 @@ inline int64_t rs_tile_rows(int ky, int Hs, int Hd) {
     return span < Hs ? span : Hs;
 }
 
+// ---- the reference's metric scripts (metrics.py: calculate_from_disk): OpenCV's INTER_CUBIC resize of float images, L1 / MAE, and the
+// uniform-window SSIM with the sample covariance ------------------------------------------------------------------------------------------------------
+// cv2.resize(float32 image, INTER_CUBIC) restated (resizeGeneric_ with HResizeCubic / VResizeCubic, float work type): per axis scale =
+// 1 / (n_out / n_in) in double, f = float((d + 0.5) scale - 0.5), s = floor(f), t = f - s in fp32, taps s - 1 .. s + 2 clamped into the image, the
+// Keys coefficients with A = -0.75 in fp32, the horizontal pass first.  No antialiasing, no rounding, no clipping.  Every fp32 / fp64 operation
+// below is a separate IEEE operation (cv_mul): a fused multiply-add would round once where OpenCV's C++ rounds twice.
+constexpr int kCvTW = 32, kCvTH = 16;           // output tile of resize_cubic_kernel
+constexpr int kCvRows = 4 * kCvTH;              // LDS rows of a tile: a contiguous span of source rows, or four rows per output row
+
+// a * b as an IEEE product of its own: under -ffp-contract=fast the backend fuses any multiply into the add that consumes it (a pragma does not
+// stop it), so the product passes through an empty asm statement, which the add cannot see through
+#ifdef PCDM_EMU
+#define PCDM_CV_OPAQUE(x) ((void)0)
+#else
+#define PCDM_CV_OPAQUE(x) asm volatile("" : "+v"(x))
+#endif
+__device__ __forceinline__ float cv_mul(float a, float b) {
+#pragma clang fp contract(off)
+    float p = a * b;
+    PCDM_CV_OPAQUE(p);
+    return p;
+}
+__device__ __forceinline__ void cv_cubic_coeffs(int d, double scale, int& s, float c[4]) {
+#pragma clang fp contract(off)
+    double fd = ((double)d + 0.5) * scale;
+    PCDM_CV_OPAQUE(fd);
+    const float f = (float)(fd - 0.5);
+    const float fl = floorf(f);
+    const float t = f - fl;
+    s = (int)fl;
+    const float A = -0.75f;
+    const float t1 = t + 1.0f, t2 = 1.0f - t;
+    c[0] = cv_mul(cv_mul(cv_mul(A, t1) - 5.0f * A, t1) + 8.0f * A, t1) - 4.0f * A;
+    c[1] = cv_mul(cv_mul(cv_mul(A + 2.0f, t) - (A + 3.0f), t), t) + 1.0f;
+    c[2] = cv_mul(cv_mul(cv_mul(A + 2.0f, t2) - (A + 3.0f), t2), t2) + 1.0f;
+    c[3] = 1.0f - c[0] - c[1] - c[2];
+}
+__device__ __forceinline__ float cv_tap4(float a, float b, float c, float d, const float* w) {
+#pragma clang fp contract(off)
+    return cv_mul(a, w[0]) + cv_mul(b, w[1]) + cv_mul(c, w[2]) + cv_mul(d, w[3]);
+}
+__device__ __forceinline__ float cv_load(const void* src, int f32, int64_t i) { return f32 ? ((const float*)src)[i] : (float)((const uint8_t*)src)[i]; }
+
+// One workgroup per 32 x 16 output tile of image `index`.  The tile's coefficient tables go to LDS first; then the horizontally filtered source
+// rows (fp32, 32 pixels x 3 channels each): the contiguous span [s(first) - 1, s(last) + 2] when it has at most 64 rows (every enlargement, and
+// reductions up to about 4 : 1), else the four tap rows of each output row (64 rows: without antialiasing an output row never reads more); then the
+// vertical pass out of LDS.  Source rows and columns are clamped into the image (edge replication), LDS rows into the staged rows.
+__global__ __launch_bounds__(256) void resize_cubic_kernel(const void* __restrict__ src, int f32, int Hs, int Ws, double scale_x, double scale_y,
+                                                           float* __restrict__ dst, int Hd, int Wd, int nchw, float divisor) {
+    __shared__ float tile[kCvRows * kCvTW * 3];
+    __shared__ float cx[kCvTW][4], cy[kCvTH][4];
+    __shared__ int sx[kCvTW], sy[kCvTH];
+    const int tid = threadIdx.x;
+    const int tx0 = blockIdx.x * kCvTW, ty0 = blockIdx.y * kCvTH;
+    const int tw = imin(kCvTW, Wd - tx0), th = imin(kCvTH, Hd - ty0);
+    if (tid < kCvTW) {
+        cv_cubic_coeffs(imin(tx0 + tid, Wd - 1), scale_x, sx[tid], cx[tid]);
+    } else if (tid >= 64 && tid < 64 + kCvTH) {
+        cv_cubic_coeffs(imin(ty0 + tid - 64, Hd - 1), scale_y, sy[tid - 64], cy[tid - 64]);
+    }
+    __syncthreads();
+    const int base = sy[0] - 1;
+    const int span = sy[th - 1] + 2 - base + 1;
+    const bool contiguous = span >= 4 && span <= kCvRows;
+    const int nrows = contiguous ? span : 4 * th;
+    const int rowe = tw * 3;
+    for (int i = tid; i < nrows * rowe; i += 256) {               // horizontal pass: (row, column, channel), the channel fastest
+        const int row = i / rowe, e = i - row * rowe;
+        const int col = e / 3, c = e - col * 3;
+        const int r = contiguous ? base + row : sy[row >> 2] - 1 + (row & 3);
+        const int64_t p = (int64_t)imin(imax(r, 0), Hs - 1) * Ws;
+        const int s = sx[col];
+        const float a0 = cv_load(src, f32, (p + imin(imax(s - 1, 0), Ws - 1)) * 3 + c);
+        const float a1 = cv_load(src, f32, (p + imin(imax(s, 0), Ws - 1)) * 3 + c);
+        const float a2 = cv_load(src, f32, (p + imin(imax(s + 1, 0), Ws - 1)) * 3 + c);
+        const float a3 = cv_load(src, f32, (p + imin(imax(s + 2, 0), Ws - 1)) * 3 + c);
+        tile[row * (kCvTW * 3) + e] = cv_tap4(a0, a1, a2, a3, cx[col]);
+    }
+    __syncthreads();
+    for (int i = tid; i < th * rowe; i += 256) {                  // vertical pass; the store index fastest in the destination's layout
+        int row, col, c;
+        if (nchw) {
+            c = i / (th * tw);
+            const int r2 = i - c * th * tw;
+            row = r2 / tw;
+            col = r2 - row * tw;
+        } else {
+            row = i / rowe;
+            const int e = i - row * rowe;
+            col = e / 3;
+            c = e - col * 3;
+        }
+        const int l0 = contiguous ? sy[row] - 1 - base : 4 * row;
+        const int e = col * 3 + c;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = tile[imin(imax(l0 + k, 0), nrows - 1) * (kCvTW * 3) + e];
+        float o = cv_tap4(v[0], v[1], v[2], v[3], cy[row]);
+        if (divisor > 0.f) o = o / divisor;
+        const int y = ty0 + row, x = tx0 + col;
+        dst[nchw ? ((int64_t)c * Hd + y) * Wd + x : ((int64_t)y * Wd + x) * 3 + c] = o;
+    }
+}
+
+// ws_ad[(n * kAdSlices + slice) * 2] = {sum |a - b|, sum (a + b)} over the slice's rows: a - b and a + b in fp32 as numpy forms them on float32
+// arrays, accumulated in fp64; uint8 inputs in integers (exact)
+constexpr int kAdSlices = 16;                   // 2 doubles per slice: N * 256 bytes, within pcdm_metrics_ws_bytes(..., sigma = 0)
+__global__ __launch_bounds__(256) void met_absdiff_kernel(MetImg cand, MetImg ref, int f32, int W, int H, double* __restrict__ ws_ad) {
+    __shared__ double red[2][4];
+    const int n = blockIdx.y, sl = blockIdx.x, tid = threadIdx.x;
+    const int rows = (H + kAdSlices - 1) / kAdSlices;
+    const int ya = sl * rows, yb = imin(H, ya + rows);
+    unsigned long long si0 = 0, si1 = 0;
+    double sd0 = 0.0, sd1 = 0.0;
+    for (int y = ya; y < yb; ++y)
+        for (int x3 = tid; x3 < 3 * W; x3 += 256) {
+            const float a = met_load(cand, f32, n, y, x3), b = met_load(ref, f32, n, y, x3);
+            if (f32) {
+                sd0 += (double)fabsf(a - b);
+                sd1 += (double)(a + b);
+            } else {
+                const int d = (int)a - (int)b;
+                si0 += (unsigned long long)(d < 0 ? -d : d);
+                si1 += (unsigned long long)((int)a + (int)b);
+            }
+        }
+    const double s0 = wave_sum_f64(f32 ? sd0 : (double)si0), s1 = wave_sum_f64(f32 ? sd1 : (double)si1);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; }
+    __syncthreads();
+    if (tid == 0) {
+        ws_ad[(n * kAdSlices + sl) * 2 + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        ws_ad[(n * kAdSlices + sl) * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
+
+__global__ void absdiff_final_kernel(const double* __restrict__ ws_ad, int N, double count, float* __restrict__ l1_out, float* __restrict__ mae_out) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = 0; i < kAdSlices; ++i) {
+        s0 += ws_ad[(n * kAdSlices + i) * 2];
+        s1 += ws_ad[(n * kAdSlices + i) * 2 + 1];
+    }
+    if (l1_out) l1_out[n] = (float)(s0 / count);
+    if (mae_out) mae_out[n] = (float)(s0 / s1);      // (0 / 0: NaN, x / 0: inf, as numpy divides)
+}
+
+// skimage.metrics.structural_similarity with its default uniform window (win_size = w = 2p + 1) and sample covariance: one workgroup per
+// (candidate, 16 x 16 output tile), one channel at a time.  LDS: the (16 + 2p)^2 halo tile of both images, centred fp32 as in ssim_tile_kernel
+// (8 (16 + 2p)^2 bytes), and the row sums of the five moments in fp64 (5 * 8 * 16 (16 + 2p) bytes): 77.1 KB at w = 51.  The window sums are plain
+// fp64 sums of the w taps per axis, divided by NP = w^2 once; covariances times NP / (NP - 1).
+constexpr int kBoxT = 16;
+constexpr int kBoxMaxP = 25;
+__host__ __device__ inline int box_smem_bytes(int p) {
+    const int T = kBoxT + 2 * p;
+    return 2 * T * T * (int)sizeof(float) + 5 * T * kBoxT * (int)sizeof(double);
+}
+__global__ __launch_bounds__(256) void ssim_box_tile_kernel(MetImg cand, MetImg ref, int N, int f32, int W, int H, int p, float data_range,
+                                                            const float* __restrict__ ws_range, double* __restrict__ ws_part) {
+    PCDM_DYN_SMEM(smem);
+    __shared__ float s_rng[4];     // candidate min, max; reference min, max
+    __shared__ double s_red[4];
+    const int n = blockIdx.z, tid = threadIdx.x;
+    const int T = kBoxT + 2 * p, w = 2 * p + 1;
+    float* tile = (float*)smem;                                              // [2][T][T]
+    double* hb = (double*)(smem + (size_t)2 * T * T * sizeof(float));        // [5][T][kBoxT]
+    if (tid < 64) {
+        const int which = tid >> 5, sl = tid & 31;
+        const int img = which ? N + (ref.img_stride ? n : 0) : n;
+        float mn = ws_range[(img * kMetSlices + sl) * 2], mx = ws_range[(img * kMetSlices + sl) * 2 + 1];
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, m, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+        }
+        if (sl == 0) { s_rng[which * 2] = mn; s_rng[which * 2 + 1] = mx; }
+    }
+    __syncthreads();
+    const float ca = 0.5f * (s_rng[0] + s_rng[1]), cb = 0.5f * (s_rng[2] + s_rng[3]);
+    const double R = data_range >= 0.f ? (double)data_range : (double)s_rng[1] - (double)s_rng[0];
+    const double c1 = (0.01 * R) * (0.01 * R), c2 = (0.03 * R) * (0.03 * R);
+    const double np = (double)w * (double)w, inv_np = 1.0 / np, cov_norm = np / (np - 1.0);
+    const int tx0 = blockIdx.x * kBoxT, ty0 = blockIdx.y * kBoxT;            // window coordinates of the halo tile's corner
+    double acc = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        for (int i = tid; i < T * T; i += 256) {
+            const int row = i / T, px = i - row * T;
+            const int gy = imin(ty0 + row, H - 1), gx = imin(tx0 + px, W - 1);   // (clamped: only tiles cut by the window's edge, outputs masked below)
+            tile[row * T + px] = met_load(cand, f32, n, gy, gx * 3 + c) - ca;
+            tile[(T + row) * T + px] = met_load(ref, f32, n, gy, gx * 3 + c) - cb;
+        }
+        __syncthreads();
+        for (int o = tid; o < T * kBoxT; o += 256) {                 // rows: sums of x, y, xx, yy, xy of the centred values over w columns
+            const int row = o / kBoxT, col = o - row * kBoxT;
+            double m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
+            for (int k = 0; k < w; ++k) {
+                const double x = tile[row * T + col + k], y = tile[(T + row) * T + col + k];
+                m0 += x; m1 += y; m2 += x * x; m3 += y * y; m4 += x * y;
+            }
+            hb[(0 * T + row) * kBoxT + col] = m0;
+            hb[(1 * T + row) * kBoxT + col] = m1;
+            hb[(2 * T + row) * kBoxT + col] = m2;
+            hb[(3 * T + row) * kBoxT + col] = m3;
+            hb[(4 * T + row) * kBoxT + col] = m4;
+        }
+        __syncthreads();
+        {                                                            // columns (one output pixel per lane), then the SSIM map
+            const int row = tid / kBoxT, col = tid - row * kBoxT;
+            double m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
+            for (int k = 0; k < w; ++k) {
+                m0 += hb[(0 * T + row + k) * kBoxT + col];
+                m1 += hb[(1 * T + row + k) * kBoxT + col];
+                m2 += hb[(2 * T + row + k) * kBoxT + col];
+                m3 += hb[(3 * T + row + k) * kBoxT + col];
+                m4 += hb[(4 * T + row + k) * kBoxT + col];
+            }
+            if (tx0 + p + col < W - p && ty0 + p + row < H - p) {
+                m0 *= inv_np; m1 *= inv_np; m2 *= inv_np; m3 *= inv_np; m4 *= inv_np;
+                const double ux = m0 + (double)ca, uy = m1 + (double)cb;
+                const double vx = cov_norm * (m2 - m0 * m0), vy = cov_norm * (m3 - m1 * m1), vxy = cov_norm * (m4 - m0 * m1);
+                acc += ((2.0 * ux * uy + c1) * (2.0 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
+            }
+        }
+        __syncthreads();
+    }
+    acc = wave_sum_f64(acc);
+    if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0)
+        ws_part[((int64_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
 __global__ void advance_step_kernel(int32_t* step) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1;
 }
@@ -1084,6 +1316,67 @@ extern "C" int pcdm_u8_to_nchw(const void* src_u8, int Hs, int Ws, int channels,
     }
     PCDM_LAUNCH(u8_to_nchw_kernel, grid1d((int64_t)win[2] * win[3] * channels, 256), dim3(256), 0, (hipStream_t)s, (const uint8_t*)src_u8, Ws, channels,
                 win[0], win[1], win[2], win[3], mode, scale, nm, out);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_resize_cubic_f32(const void* src, int src_is_f32, int Hs, int Ws, int channels, float* dst, int N, int Hd, int Wd, int index,
+                                     int nchw, float divisor, pcdm_stream_t s) {
+    if (!src || !dst || channels != 3 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || N <= 0 || index < 0 || index >= N) return -1;
+    if (((uintptr_t)dst & 3) || (src_is_f32 && ((uintptr_t)src & 3))) return -1;
+    if ((int64_t)Hs * Ws * 3 >= (int64_t)1 << 31 || (int64_t)Hd * Wd * 3 >= (int64_t)1 << 31 || (Hd + kCvTH - 1) / kCvTH > 65535) return -1;
+    const double scale_x = 1.0 / ((double)Wd / (double)Ws), scale_y = 1.0 / ((double)Hd / (double)Hs);
+    PCDM_LAUNCH(resize_cubic_kernel, dim3((Wd + kCvTW - 1) / kCvTW, (Hd + kCvTH - 1) / kCvTH), dim3(256), 0, (hipStream_t)s, src, src_is_f32 != 0, Hs, Ws,
+                scale_x, scale_y, dst + (int64_t)index * Hd * Wd * 3, Hd, Wd, nchw != 0, divisor);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_absdiff(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr,
+                            const int32_t* ref_win, int channels, int is_f32, float* l1, float* mae, void* ws, int64_t ws_bytes, pcdm_stream_t s) {
+    if (!met_args_ok(cand, N, Hc, Wc, cand_win, ref, ref_n, Hr, Wr, ref_win, channels) || (!l1 && !mae) || !ws || ((uintptr_t)ws & 7)) return -1;
+    const int W = cand_win[2], H = cand_win[3];
+    if (ws_bytes < pcdm_metrics_ws_bytes(N, ref_n, W, H, 0.f)) return -1;     // (N * kAdSlices * 2 doubles = N * 256 bytes: never more than that)
+    const MetImg ci = met_img(cand, 0, Hc, Wc, cand_win), ri = met_img(ref, ref_n, Hr, Wr, ref_win);
+    PCDM_LAUNCH(met_absdiff_kernel, dim3(kAdSlices, N), dim3(256), 0, (hipStream_t)s, ci, ri, is_f32, W, H, (double*)ws);
+    PCDM_CHECK_LAUNCH();
+    PCDM_LAUNCH(absdiff_final_kernel, grid1d(N, 64), dim3(64), 0, (hipStream_t)s, (const double*)ws, N, 3.0 * (double)W * (double)H, l1, mae);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t pcdm_ssim_box_ws_bytes(int N, int ref_n, int W, int H, int win_size) {
+    if (N <= 0 || N > 65535 || (ref_n != 1 && ref_n != N) || W <= 0 || H <= 0) return -1;
+    if (win_size < 3 || win_size > 2 * kBoxMaxP + 1 || !(win_size & 1) || W < win_size || H < win_size) return -1;
+    const int64_t tiles = (int64_t)((W - win_size + 1 + kBoxT - 1) / kBoxT) * ((H - win_size + 1 + kBoxT - 1) / kBoxT);
+    return (int64_t)(N + ref_n) * kMetSlices * 2 * sizeof(float) + (int64_t)N * tiles * sizeof(double);
+}
+
+extern "C" int pcdm_ssim_box(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr,
+                             const int32_t* ref_win, int channels, int is_f32, int win_size, float data_range, float* scores, void* ws,
+                             int64_t ws_bytes, pcdm_stream_t s) {
+    if (!met_args_ok(cand, N, Hc, Wc, cand_win, ref, ref_n, Hr, Wr, ref_win, channels) || !scores || !ws || ((uintptr_t)ws & 7)) return -1;
+    const int W = cand_win[2], H = cand_win[3];
+    const int64_t need = pcdm_ssim_box_ws_bytes(N, ref_n, W, H, win_size);
+    if (need < 0 || ws_bytes < need) return -1;
+    const int p = (win_size - 1) / 2;
+    const int gx = (W - 2 * p + kBoxT - 1) / kBoxT, gy = (H - 2 * p + kBoxT - 1) / kBoxT;
+    if (gy > 65535) return -1;
+    const MetImg ci = met_img(cand, 0, Hc, Wc, cand_win), ri = met_img(ref, ref_n, Hr, Wr, ref_win);
+    float* ws_range = (float*)ws;
+    double* ws_part = (double*)((char*)ws + (size_t)(N + ref_n) * kMetSlices * 2 * sizeof(float));
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)ssim_box_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, box_smem_bytes(kBoxMaxP));
+        attr_done = true;
+    }
+    PCDM_LAUNCH(met_range_kernel, dim3(kMetSlices, N + ref_n), dim3(256), 0, (hipStream_t)s, ci, ri, N, is_f32, W, H, ws_range);
+    PCDM_CHECK_LAUNCH();
+    PCDM_LAUNCH(ssim_box_tile_kernel, dim3(gx, gy, N), dim3(256), box_smem_bytes(p), (hipStream_t)s, ci, ri, N, is_f32, W, H, p, data_range, ws_range,
+                ws_part);
+    PCDM_CHECK_LAUNCH();
+    PCDM_LAUNCH(ssim_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, ws_part, N, gx * gy, 1.0 / (3.0 * (double)(W - 2 * p) * (double)(H - 2 * p)),
+                scores, (int32_t*)nullptr);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

@@ -19,6 +19,11 @@ packages on their checkpoints is NOT pinned by a test here -- the same standing 
 metrics.py:23-257): the InceptionV3 trunk in exact fp32 and the fp64 statistics on the device (include/pcdm.h: pcdm_inception_features,
 pcdm_fid_accumulate, pcdm_fid_finalize), the Frechet distance itself on the host in fp64.  Same standing: restated, checked on synthetic weights
 (tests/test_fid.py), parity with torchvision's checkpoint not pinned.
+
+``l1`` / ``mae`` / ``ssim_box`` are the remaining per-pair numbers of the reference's metric scripts (metrics.py: compare_l1, compare_mae and the
+``ssim`` array: skimage's uniform 51 x 51 window with the sample covariance; include/pcdm.h: pcdm_absdiff, pcdm_ssim_box);
+tools/calculate_metrics.py is the whole script.  Same standing: restated, checked against fp64 (tests/test_eval_metrics.py), scikit-image parity
+not pinned.
 """
 from __future__ import annotations
 
@@ -75,6 +80,37 @@ def mse(cand: torch.Tensor, ref: torch.Tensor, *, cand_window: Window = None, re
     out = torch.empty(cand.shape[0], dtype=torch.float32, device=cand.device)
     ops.psnr(cand, ref, cw, rw, out, None, _workspace(cand, ref, cw, 0.0), data_range=255.0)
     return out
+
+
+def l1(cand: torch.Tensor, ref: torch.Tensor, *, cand_window: Window = None, ref_window: Window = None) -> torch.Tensor:
+    """fp32 [N] on the device: the reference's ``compare_l1``, ``mean |a - b|`` per candidate (fp64 sums; exact integer sums for uint8)."""
+    cand, ref, cw, rw = _prep(cand, ref, cand_window, ref_window)
+    out = torch.empty(cand.shape[0], dtype=torch.float32, device=cand.device)
+    ops.absdiff(cand, ref, cw, rw, out, None, _workspace(cand, ref, cw, 0.0))
+    return out
+
+
+def mae(cand: torch.Tensor, ref: torch.Tensor, *, cand_window: Window = None, ref_window: Window = None) -> torch.Tensor:
+    """fp32 [N] on the device: the reference's ``compare_mae``, ``sum |a - b| / sum (a + b)`` per candidate; NaN or inf where the denominator is
+    zero, as numpy divides."""
+    cand, ref, cw, rw = _prep(cand, ref, cand_window, ref_window)
+    out = torch.empty(cand.shape[0], dtype=torch.float32, device=cand.device)
+    ops.absdiff(cand, ref, cw, rw, None, out, _workspace(cand, ref, cw, 0.0))
+    return out
+
+
+def ssim_box(cand: torch.Tensor, ref: torch.Tensor, *, win_size: int = 51, data_range: Optional[float] = None, cand_window: Window = None,
+             ref_window: Window = None) -> torch.Tensor:
+    """fp32 [N] on the device: ``skimage.metrics.structural_similarity(ref, cand[n], win_size=win_size, data_range=data_range, channel_axis=2)``
+    with skimage's defaults -- a ``win_size`` x ``win_size`` uniform window and the sample covariance; the ``ssim`` array of the reference's
+    ``<W>_<H>_metrics.npz`` (win_size 51, data_range 1).  ``win_size`` odd, 3 .. 51, not larger than the window; ``data_range`` None: max - min of
+    the candidate's window.  scikit-image is not a dependency: restated and checked against an fp64 restatement (tests/test_eval_metrics.py),
+    parity with the package itself NOT pinned -- the same standing as LPIPS and FID."""
+    cand, ref, cw, rw = _prep(cand, ref, cand_window, ref_window)
+    n = ops.ssim_box_ws_bytes(cand.shape[0], ref.shape[0], cw[2], cw[3], win_size)
+    ws = torch.empty(max(n, 8) // 8, dtype=torch.float64, device=cand.device)     # (a refused problem still reaches the library: -1, nothing written)
+    scores = torch.empty(cand.shape[0], dtype=torch.float32, device=cand.device)
+    return ops.ssim_box(cand, ref, cw, rw, scores, ws, win_size=win_size, data_range=data_range)
 
 
 def pick_best(cand: torch.Tensor, ref: torch.Tensor, *, cand_window: Window = None, ref_window: Window = None, sigma: float = 1.2,

@@ -953,6 +953,39 @@ def psnr(cand: torch.Tensor, ref: torch.Tensor, cand_win: Sequence[int], ref_win
     return out
 
 
+def absdiff(cand: torch.Tensor, ref: torch.Tensor, cand_win: Sequence[int], ref_win: Sequence[int], l1: Optional[torch.Tensor],
+            mae: Optional[torch.Tensor], ws: torch.Tensor) -> None:
+    """l1 / mae fp32 [N]: mean |a - b| and sum |a - b| / sum (a + b) over the windows (include/pcdm.h: pcdm_absdiff); ws as for ``psnr``."""
+    f32 = _images(cand, ref)
+    for t in (l1, mae):
+        if t is not None:
+            _c(t, torch.float32)
+    N, W, H = cand.shape[0], int(cand_win[2]), int(cand_win[3])
+    call = lambda: _lib.lib().pcdm_absdiff(_ptr(cand), N, cand.shape[1], cand.shape[2], _win(cand_win), _ptr(ref), ref.shape[0], ref.shape[1],  # noqa: E731
+                                           ref.shape[2], _win(ref_win), cand.shape[3], f32, _ptr(l1), _ptr(mae), _ptr(ws),
+                                           ws.numel() * ws.element_size(), _stream(cand))
+    _chk(_launch(cand, call, "absdiff", 3.0 * N * W * H * 3, (N, H, W, f32)), "pcdm_absdiff")
+
+
+def ssim_box_ws_bytes(N: int, ref_n: int, W: int, H: int, win_size: int) -> int:
+    """Workspace bytes of ``ssim_box``; -1: the library refuses the problem."""
+    return int(_lib.lib().pcdm_ssim_box_ws_bytes(N, ref_n, W, H, int(win_size)))
+
+
+def ssim_box(cand: torch.Tensor, ref: torch.Tensor, cand_win: Sequence[int], ref_win: Sequence[int], scores: torch.Tensor, ws: torch.Tensor, *,
+             win_size: int = 51, data_range: Optional[float] = None) -> torch.Tensor:
+    """scores fp32 [N]: skimage's uniform-window SSIM with the sample covariance (include/pcdm.h: pcdm_ssim_box).  data_range None: max - min of
+    each candidate's window."""
+    f32 = _images(cand, ref)
+    _c(scores, torch.float32)
+    N, W, H, w = cand.shape[0], int(cand_win[2]), int(cand_win[3]), int(win_size)
+    call = lambda: _lib.lib().pcdm_ssim_box(_ptr(cand), N, cand.shape[1], cand.shape[2], _win(cand_win), _ptr(ref), ref.shape[0], ref.shape[1],  # noqa: E731
+                                            ref.shape[2], _win(ref_win), cand.shape[3], f32, w, -1.0 if data_range is None else float(data_range),
+                                            _ptr(scores), _ptr(ws), ws.numel() * ws.element_size(), _stream(cand))
+    _chk(_launch(cand, call, "ssim_box", 10.0 * N * 3 * max(W - w + 1, 0) * max(H - w + 1, 0) * 2 * w, (N, H, W, w)), "pcdm_ssim_box")
+    return scores
+
+
 def select_image(cand: torch.Tensor, win: Sequence[int], index: torch.Tensor, out: torch.Tensor, normalized: bool) -> torch.Tensor:
     """out <- the window of cand[index[0]] (uint8 [N, Hc, Wc, 3]; index int32 on the device): uint8 [H, W, 3], or fp32 [1, 3, H, W] =
     (x / 255 - 0.5) / 0.5 when ``normalized`` (include/pcdm.h: pcdm_select_image)."""
@@ -1171,3 +1204,19 @@ def u8_to_nchw(src: torch.Tensor, win: Sequence[int], out: torch.Tensor, *, mode
     _chk(_lib.lib().pcdm_u8_to_nchw(_ptr(src), src.shape[0], src.shape[1], Cn, _win(win), int(mode), float(scale), (C.c_float * Cn)(*mean),
                                     (C.c_float * Cn)(*std), _ptr(out), _stream(src)), "pcdm_u8_to_nchw")
     return out
+
+
+def resize_cubic_f32(src: torch.Tensor, dst: torch.Tensor, index: int, *, nchw: bool, divisor: float = 0.0) -> torch.Tensor:
+    """src uint8 / fp32 [Hs, Ws, 3] -> image ``index`` of the fp32 batch dst, [N, Hd, Wd, 3] or (``nchw``) [N, 3, Hd, Wd]: OpenCV's INTER_CUBIC
+    for float images, divided by ``divisor`` when it is positive (include/pcdm.h: pcdm_resize_cubic_f32)."""
+    assert src.dim() == 3 and dst.dim() == 4 and src.dtype in (torch.uint8, torch.float32) and src.is_contiguous() and src.device == dst.device, \
+        (src.shape, src.dtype, dst.shape)
+    _c(dst, torch.float32)
+    N = dst.shape[0]
+    chan, Hd, Wd = (dst.shape[1], dst.shape[2], dst.shape[3]) if nchw else (dst.shape[3], dst.shape[1], dst.shape[2])
+    if chan != src.shape[2]:
+        raise ValueError(f"source {tuple(src.shape)} and destination {tuple(dst.shape)} ({'NCHW' if nchw else 'NHWC'}) differ in channels")
+    call = lambda: _lib.lib().pcdm_resize_cubic_f32(_ptr(src), int(src.dtype == torch.float32), src.shape[0], src.shape[1], src.shape[2], _ptr(dst),  # noqa: E731
+                                                    N, Hd, Wd, int(index), int(bool(nchw)), float(divisor), _stream(src))
+    _chk(_launch(src, call, "resize_cubic", 2.0 * 3 * Hd * Wd * 8 * 2, (src.shape[0], src.shape[1], Hd, Wd)), "pcdm_resize_cubic_f32")
+    return dst

@@ -168,3 +168,35 @@ def stage3_inputs(s_img: torch.Tensor, gen_t_img: torch.Tensor, W: int, H: int) 
     """The stage-3 driver's per-pair tensors: ``(vae_gen_t_image, s_img_u8)`` -- the stage-2 result resized and normalised, fp32 ``[1, 3, H, W]``,
     and the resized source, uint8 ``[H, W, 3]``, for ``clip_pixel_values``."""
     return to_tensor_normalized(resize(gen_t_img, (W, H))), resize(s_img, (W, H))
+
+
+def resize_cv_cubic(image: torch.Tensor, size: Sequence[int], *, divisor: Optional[float] = None, layout: str = "nhwc",
+                    out: Optional[torch.Tensor] = None, index: int = 0) -> torch.Tensor:
+    """``cv2.resize(image.astype(np.float32), size, interpolation=cv2.INTER_CUBIC)`` (``/ divisor`` when given) on the device -- the resize the
+    reference's metric scripts put in front of every metric (metrics.py: calculate_from_disk).  ``image``: uint8 or fp32 ``[H, W, 3]``; ``size`` is
+    ``(width, height)`` as in OpenCV.  The result is fp32, not rounded and not clipped (it overshoots below 0 and above 255), written as image
+    ``index`` of the batch ``out``: ``[N, size[1], size[0], 3]`` for ``layout="nhwc"`` (SSIM, PSNR, L1, MAE) or ``[N, 3, size[1], size[0]]`` for
+    ``"nchw"`` (LPIPS, FID); without ``out`` a batch of one is allocated.  The batch is returned; its other images are not touched.
+
+    This is a different resampler from ``resize`` (Pillow's): no antialiasing when reducing, A = -0.75, fp32 arithmetic.  OpenCV is not a dependency:
+    the algorithm is restated (include/pcdm.h: pcdm_resize_cubic_f32) and checked against an fp64 restatement (tests/test_eval_metrics.py), so
+    parity with the ``cv2`` package itself is NOT pinned by a test here -- the same standing as LPIPS and FID.  One launch, no host synchronisation."""
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"layout must be 'nhwc' or 'nchw', not {layout!r}")
+    if image.dim() != 3 or image.shape[2] != 3 or image.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"an image is uint8 or fp32 [H, W, 3]: got {image.dtype} {tuple(image.shape)}")
+    Wd, Hd = int(size[0]), int(size[1])
+    if Wd <= 0 or Hd <= 0:
+        raise ValueError(f"size must be positive: {tuple(size)}")
+    if divisor is not None and not divisor > 0:
+        raise ValueError(f"divisor must be positive: {divisor!r}")
+    shape = (Hd, Wd, 3) if layout == "nhwc" else (3, Hd, Wd)
+    if out is None:
+        if index != 0:
+            raise ValueError("index= needs out=")
+        out = torch.empty((1, *shape), dtype=torch.float32, device=image.device)
+    elif out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[1:]) != shape or not out.is_contiguous() or out.device != image.device:
+        raise ValueError(f"out must be a contiguous fp32 [N, {', '.join(str(v) for v in shape)}] batch on {image.device}")
+    if not 0 <= int(index) < out.shape[0]:
+        raise ValueError(f"index {index} outside the batch of {out.shape[0]}")
+    return ops.resize_cubic_f32(image.contiguous(), out, int(index), nchw=layout == "nchw", divisor=0.0 if divisor is None else float(divisor))

@@ -7,8 +7,8 @@ and, with ``--fid-weights``, the FID of ALL generated images against a real set.
 
 Each argument is a directory (its image files, sorted by name), a ``.txt`` list of paths, or one image file.  Files are decoded with PIL and
 scored AS THEY ARE: the images of a pair, and all pairs, must have one size.  The reference resizes every image with
-``cv2.resize(..., INTER_CUBIC)`` first; that resampler is NOT restated here -- OpenCV is not a dependency of this project and its output could
-not be checked -- so resize beforehand if the files are not at the evaluation size (``pcdms_amd.preprocess`` has Pillow's resampler on the device).
+``cv2.resize(..., INTER_CUBIC)`` first: ``tools/calculate_metrics.py`` is the tool that does that (the reference's metric scripts as a whole, with
+its pairing, MAE, L1 and the uniform-window SSIM); this one scores files that already are at the evaluation size.
 SSIM is the reference's ``ssim_256`` (sigma 1.2, data range = max - min of the generated image); LPIPS follows the reference in feeding [0, 1]
 images without the [-1, 1] remap unless ``--normalize`` is given (pcdms_amd/metrics.py: LPIPS).  FID is the reference's: InceptionV3 pool3
 features of the bilinearly resized (299 x 299) images with its [0, 1]-input remap quirk, fp64 statistics, Frechet distance
