@@ -3,7 +3,7 @@
 The reference's drivers decode N samples per pair, copy them to the host and keep the one with the best
 ``skimage.metrics.structural_similarity(..., gaussian_weights=True, sigma=1.2, use_sample_covariance=False)`` against the target
 (stage2_batchtest_inpaint_model.py:203-219).  Here the decoded uint8 NHWC batch (``output_type="uint8"``) is scored where it lies by the HIP
-kernels of csrc/misc.hip (include/pcdm.h: pcdm_ssim / pcdm_psnr / pcdm_select_image); nothing in this module synchronises with the host, so
+kernels of csrc/image_metrics.hip (include/pcdm.h: pcdm_ssim / pcdm_psnr / pcdm_select_image); nothing in this module synchronises with the host, so
 ``pick_best`` can sit in the middle of a device-resident chain or inside a captured graph.
 
 Images are NHWC with 3 channels, uint8 or fp32 (candidates and reference the same type): ``cand`` [N, H, W, 3] (or [H, W, 3]), ``ref``
@@ -11,12 +11,12 @@ Images are NHWC with 3 channels, uint8 or fp32 (candidates and reference the sam
 [source | target] canvas is scored against a stand-alone target with no crop copy.
 
 ``LPIPS`` is the paper's second per-pair metric (the reference's metrics.py calls the ``lpips`` package): LPIPS v0.1 with the AlexNet trunk in
-exact fp32 on the fp32-input MFMA (include/pcdm.h: pcdm_lpips).  Neither ``lpips`` nor ``torchvision`` is a dependency: the network is restated
+exact fp32 on the fp32-input MFMA (csrc/eval_nets.hip; include/pcdm.h: pcdm_lpips).  Neither ``lpips`` nor ``torchvision`` is a dependency: the network is restated
 from its published definition and checked against an fp64 restatement with synthetic weights (tests/test_lpips.py), so parity with the upstream
 packages on their checkpoints is NOT pinned by a test here -- the same standing as the diffusers restatements.
 
 ``InceptionV3Features`` / ``FIDStatistics`` / ``frechet_distance`` / ``FID`` are the third metric, the reference's FID (inception.py,
-metrics.py:23-257): the InceptionV3 trunk in exact fp32 and the fp64 statistics on the device (include/pcdm.h: pcdm_inception_features,
+metrics.py:23-257): the InceptionV3 trunk in exact fp32 and the fp64 statistics on the device (csrc/eval_nets.hip; include/pcdm.h: pcdm_inception_features,
 pcdm_fid_accumulate, pcdm_fid_finalize), the Frechet distance itself on the host in fp64.  Same standing: restated, checked on synthetic weights
 (tests/test_fid.py), parity with torchvision's checkpoint not pinned.
 

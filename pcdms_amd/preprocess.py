@@ -3,7 +3,7 @@ CLIP processor's pixel values, from the decoded uint8 pixels.
 
 Per pair the reference's stage-2 driver resizes four images with ``Image.resize((W, H), Image.BICUBIC)``, pastes two canvases, normalises them
 and runs ``CLIPImageProcessor()`` on the source, all on the host (stage2_batchtest_inpaint_model.py:135-149).  Here the decoded image is uploaded once
-as uint8 ``[H, W, 3]`` and everything after it is the HIP kernels of csrc/misc.hip (include/pcdm.h: pcdm_resample_u8 / pcdm_u8_to_nchw).  Pillow's
+as uint8 ``[H, W, 3]`` and everything after it is the HIP kernels of csrc/image_prep.hip (include/pcdm.h: pcdm_resample_u8 / pcdm_u8_to_nchw).  Pillow's
 8-bit resampler is integer arithmetic (22-bit fixed-point weights, a horizontal pass rounded to uint8, then a vertical pass), so the bytes are
 Pillow's bytes, and the two float conversions repeat the operation order of their host originals, so the fp32 tensors are bit-identical as well.
 

@@ -8,14 +8,18 @@ from __future__ import annotations
 import ctypes
 import shutil
 import subprocess
+import sys
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent.parent
+if str(ROOT) not in sys.path:      # (run as a script)
+    sys.path.insert(0, str(ROOT))
+from pcdms_amd.build import SOURCES, write_tuning_include  # noqa: E402  (the product build's list: both libraries hold the same units)
+
 CSRC = ROOT / "pcdms_amd" / "csrc"
 OUT = HERE / "_build"
 LIB = OUT / "libpcdm_emu.so"
-SOURCES = ["norm.hip", "gemm.hip", "gemm_ext.hip", "rowgemm.hip", "attn.hip", "misc.hip", "unet_ctx.hip"]
 
 
 def _cxx() -> str:
@@ -27,15 +31,16 @@ def _cxx() -> str:
 
 def build(force: bool = False) -> Path:
     OUT.mkdir(exist_ok=True)
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "pcdm_device.h", CSRC / "gemm_args.h", CSRC / "gemm_kernel.inc", ROOT / "include" / "pcdm.h", HERE / "hip_emu.h",
-                                          HERE / "hip_emu.cpp", ROOT / "pcdms_amd" / "tuning" / "gfx950.json"]
+    # every source file of csrc/ (units, headers, includes: none can be forgotten; tuning_table.inc is rewritten only when its content changes), the
+    # C header, the emulator and the tuning table's source
+    deps = [*(f for f in CSRC.iterdir() if f.suffix in (".hip", ".h", ".inc")), ROOT / "include" / "pcdm.h", HERE / "hip_emu.h", HERE / "hip_emu.cpp",
+            ROOT / "pcdms_amd" / "tuning" / "gfx950.json"]
     if not force and LIB.exists() and all(d.stat().st_mtime <= LIB.stat().st_mtime for d in deps):
         return LIB
-    from pcdms_amd.build import write_tuning_include
     write_tuning_include()        # (csrc/tuning_table.inc: included by unet_ctx.hip)
     cxx = _cxx()
     objs = []
-    common = ["-O2", "-std=c++17", "-fPIC", "-DPCDM_EMU", "-Wno-unknown-attributes", "-Wno-unused-value"]
+    common = ["-O2", "-std=c++17", "-fPIC", "-DPCDM_EMU", "-DPCDM_EMU_UNITS", "-Wno-unknown-attributes", "-Wno-unused-value"]   # (UNITS: misc.hip)
     for s in SOURCES:
         o = OUT / (s + ".o")
         subprocess.check_call([cxx, *common, "-x", "c++", "-include", str(HERE / "hip_emu.h"), "-c", str(CSRC / s),

@@ -43,6 +43,14 @@ def test_emulator_exports_every_symbol():
     assert lib.pcdm_is_emulator() == 1
 
 
+def test_every_build_compiles_every_source():
+    """pcdms_amd/build.py's SOURCES is the one list of translation units: it names every csrc/*.hip, and the emulator build reads that list."""
+    from pcdms_amd import build
+    from tests.emu import build_emu
+    assert {p.name for p in build.CSRC.glob("*.hip")} == set(build.SOURCES)
+    assert build_emu.SOURCES is build.SOURCES
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from pcdms_amd import _lib
     with pytest.raises(RuntimeError, match="no fallback"):

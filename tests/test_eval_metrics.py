@@ -1,4 +1,4 @@
-"""The reference's metric scripts on the device (tools/calculate_metrics.py): OpenCV's INTER_CUBIC float resize, L1 / MAE and the uniform-window
+"""The reference's metric scripts on the device (tools/calculate_metrics.py; csrc/image_prep.hip, csrc/image_metrics.hip): OpenCV's INTER_CUBIC float resize, L1 / MAE and the uniform-window
 SSIM with the sample covariance, each against an fp64 restatement written here.  OpenCV and scikit-image are not dependencies; parity with the
 packages themselves is not pinned.
 

@@ -1,4 +1,4 @@
-"""Device-side FID (pcdms_amd/metrics.py: InceptionV3Features, FIDStatistics, frechet_distance, FID; csrc/misc.hip: pcdm_inception_features,
+"""Device-side FID (pcdms_amd/metrics.py: InceptionV3Features, FIDStatistics, frechet_distance, FID; csrc/eval_nets.hip: pcdm_inception_features,
 pcdm_conv2d_f32_ex, the pools, pcdm_inception_input, pcdm_fid_accumulate / _finalize).
 
 The yardstick is an fp64 restatement of torchvision's ``inception_v3`` trunk with ``torch.nn.functional`` on the CPU (``_trunk`` below) on synthetic

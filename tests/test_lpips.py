@@ -1,4 +1,4 @@
-"""Device-side LPIPS v0.1 (AlexNet) in exact fp32 (pcdms_amd/metrics.py: LPIPS; csrc/misc.hip: pcdm_lpips / pcdm_conv2d_f32 / pcdm_maxpool3s2_f32).
+"""Device-side LPIPS v0.1 (AlexNet) in exact fp32 (pcdms_amd/metrics.py: LPIPS; csrc/eval_nets.hip: pcdm_lpips / pcdm_conv2d_f32 / pcdm_maxpool3s2_f32).
 
 The yardstick is an fp64 restatement of the network with ``torch.nn.functional`` on the CPU (``_net`` below), on synthetic seeded weights:
 neither the ``lpips`` package nor ``torchvision`` nor a real checkpoint is available, so parity with upstream on its weights is not pinned here.

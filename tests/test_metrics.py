@@ -1,4 +1,4 @@
-"""Device-side SSIM / PSNR and the best-of-N pick (pcdms_amd/metrics.py, csrc/misc.hip: pcdm_ssim / pcdm_psnr / pcdm_select_image).
+"""Device-side SSIM / PSNR and the best-of-N pick (pcdms_amd/metrics.py, csrc/image_metrics.hip: pcdm_ssim / pcdm_psnr / pcdm_select_image).
 
 The yardstick is an fp64 restatement, written here with numpy only, of
 ``skimage.metrics.structural_similarity(ref, cand, gaussian_weights=True, sigma=s, use_sample_covariance=False, channel_axis=2, data_range=R)``:

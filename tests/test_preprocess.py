@@ -1,4 +1,4 @@
-"""Device-side input preparation (pcdms_amd/preprocess.py, csrc/misc.hip: pcdm_resample_u8 / pcdm_u8_to_nchw).
+"""Device-side input preparation (pcdms_amd/preprocess.py, csrc/image_prep.hip: pcdm_resample_u8 / pcdm_u8_to_nchw).
 
 The yardsticks are the installed libraries the drivers call on the host: ``Image.resize(..., Image.BICUBIC)`` of Pillow, the drivers' own
 ``to_tensor_normalized`` and ``transformers.CLIPImageProcessor()``.  Pillow's 8-bit resampler is integer arithmetic, so the tolerance of every
