@@ -504,6 +504,49 @@ int64_t pcdm_ssim_box_ws_bytes(int N, int ref_n, int W, int H, int win_size);
 int pcdm_ssim_box(const void* cand, int N, int Hc, int Wc, const int32_t* cand_win, const void* ref, int ref_n, int Hr, int Wr, const int32_t* ref_win,
                   int channels, int is_f32, int win_size, float data_range, float* scores, void* ws, int64_t ws_bytes, pcdm_stream_t s);
 
+/* ---- DWPose pose maps from keypoints: what controlnet_aux's DWposeDetector.__call__ does after its networks (dwpose/__init__.py:55-87 -> draw_pose
+ * -> util.draw_bodypose / draw_handpose / draw_facepose, then cv2.resize(..., INTER_LINEAR)), on the device.  OpenCV is not a dependency: the
+ * arithmetic from keypoints to integers repeats the reference's, but the RASTER RULES below are this library's own statement of OpenCV's
+ * ellipse2Poly + fillConvexPoly, circle and line; parity with the cv2 package is NOT pinned by a test here (tests/test_pose.py pins the rules
+ * against Pillow's rasteriser) -- the same standing as pcdm_resize_cubic_f32.
+ * pcdm_pose_draw: keypoints fp32 [M, P, 134, 2] (x, y in pixels of the Wd x Hd detection frame), scores fp32 [M, P, 134], OpenPose order (what
+ *   Wholebody.__call__ returns: 18 body joints, 6 feet, 68 face, 21 left hand, 21 right hand); a map with fewer persons is padded with score 0.
+ *   out uint8 [M, Hd, Wd, 3], every byte written.  tables: int32[740] in DEVICE memory, filled on the host by pcdm_pose_tables and uploaded by the
+ *   caller; ws: pcdm_pose_ws_bytes(M, P) bytes, 4-byte aligned (NULL when P = 0).  Two launches, no atomics, no host synchronisation; the result
+ *   does not depend on launch order.  Returns -1 and writes nothing for P > 32, a side above 4096, M > 65535 or a missing pointer.
+ *   Pass 1 fills a table of 185 slots per person in DRAW ORDER, empty where the reference draws nothing: limbs (for i < 17: for person),
+ *   joints (for i < 18: for person), all left hands then all right hands (20 edges then 21 points each; hands = 0: none), face points
+ *   (faces = 0: none; the reference has that call commented out).  Arithmetic, every operation its own IEEE operation (no contraction, true
+ *   division, correctly rounded sqrt): c = k / float(W or H) in fp32; a body joint is visible iff score > 0.3f; a hand or face point with
+ *   score < 0.3f becomes c = -1.  Joint: disc of radius 4 at (int(c_x * W), int(c_y * H)) (fp32 product, truncated), colour table[i], no
+ *   coordinate test.  Limb i (both joints visible): Y = c_x * float(W), X = c_y * float(H) in fp32, centre (int((Y0 + Y1) / 2), int((X0 + X1) / 2)),
+ *   a = int(sqrt((X0 - X1)^2 + (Y0 - Y1)^2) / 2) in fp32, theta = int(atan2(X0 - X1, Y0 - Y1) * (180.0 / pi)) in double, colour table[i].  Hand
+ *   edge e: a line between its two points (int(c_x * W), int(c_y * H)) if all four integers are >= 1, colour rint(hsv_to_rgb(e / 20, 1, 1) * 255);
+ *   hand point: disc of radius 1, (0, 0, 255), if both integers are >= 1; face point: radius 3, white, same test.  Integers are clamped to
+ *   +-2^20 (NaN: the lower bound), so any float is a valid keypoint.
+ *   Pass 2: a workgroup owns a 32 x 8 pixel tile of one map, keeps the slots that can touch it (in order, in LDS) and every pixel takes the LAST
+ *   slot that covers it: a limb as colour * 3 / 5 per channel (the canvas * 0.6 the reference applies after the limb layer), anything else as
+ *   is; uncovered pixels are 0.  Coverage of pixel (x, y), integers only, dx = x - cx, dy = y - cy:
+ *     limb:  C = lround(cos(theta deg) * 16384), S = lround(sin(theta deg) * 16384) (pcdm_pose_tables, double), u = 2 (dx C + dy S),
+ *            v = 2 (dy C - dx S), A = 2 a + 1, B = 9: |u| <= A * 16384 and |v| <= B * 16384 and B^2 u^2 + A^2 v^2 <= A^2 B^2 2^28 -- the ellipse of
+ *            half-axes (a, 4) inflated by half a pixel (fillConvexPoly paints the outline too); a = 0 needs no special case.  The last test is
+ *            evaluated in 128 bits, so no a overflows it.
+ *     disc of radius r:  dx^2 + dy^2 <= r^2 + r / 2 (integer division).
+ *     line (x0, y0) - (x1, y1), one pixel wide: the major axis is x when |x1 - x0| >= |y1 - y0|; with n = the major |delta| and k = 0 .. n the
+ *            major coordinate is start + sgn * k and the minor one start + sgn * floor((2 k |minor delta| + n) / (2 n)); evaluated per pixel.
+ * pcdm_pose_tables: fills HOST int32[count = 740]: {C, S} of 0 .. 359 degrees, then the 20 hand-edge colours as r | g << 8 | b << 16
+ *   (matplotlib's hsv_to_rgb in double, rounded half to even).
+ * pcdm_resize_linear_u8: cv2.resize(uint8 image, (Wd, Hd), interpolation=cv2.INTER_LINEAR) in OpenCV's 8-bit fixed-point form, src
+ *   [M, Hs, Ws, 3] -> dst [M, Hd, Wd, 3].  Per axis scale = 1.0 / ((double)n_out / (double)n_in), f = (float)((d + 0.5) * scale - 0.5), s = floor(f),
+ *   t = f - s in fp32; weights w0 = rint((1 - t) * 2048), w1 = rint(t * 2048).  Horizontally an index outside [0, n_in - 2] is clamped and its
+ *   t set to 0; vertically the two rows s, s + 1 are clamped into the image and t is kept.  S = src[s] w0 + src[s + 1] w1 in int per row,
+ *   out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Equal sizes copy.  One launch; -1 for non-positive sizes or 2^31 bytes. */
+int pcdm_pose_tables(int32_t* tables, int count);
+int64_t pcdm_pose_ws_bytes(int M, int P);
+int pcdm_pose_draw(const float* keypoints, const float* scores, int M, int P, int Hd, int Wd, int hands, int faces, const int32_t* tables, void* out,
+                   void* ws, int64_t ws_bytes, pcdm_stream_t s);
+int pcdm_resize_linear_u8(const void* src, int M, int Hs, int Ws, void* dst, int Hd, int Wd, pcdm_stream_t s);
+
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host
  * that is not Python: pcdm_unet_create from the topology, pcdm_unet_set_weight / _set_vector with the packed tensors under their

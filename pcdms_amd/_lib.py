@@ -143,6 +143,10 @@ _SIGS = {
     "pcdm_absdiff": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_ssim_box_ws_bytes": ([_I, _I, _I, _I, _I], _L),
     "pcdm_ssim_box": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _I, _F, _P, _P, _L, _P], C.c_int),
+    "pcdm_pose_tables": ([C.POINTER(C.c_int32), _I], C.c_int),
+    "pcdm_pose_ws_bytes": ([_I, _I], _L),
+    "pcdm_pose_draw": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_resize_linear_u8": ([_P, _I, _I, _I, _P, _I, _I, _P], C.c_int),
     "pcdm_unet_create":([C.POINTER(UNetConfig)], _P),
     "pcdm_unet_destroy": ([_P], None),
     "pcdm_unet_last_error": ([_P], C.c_char_p),

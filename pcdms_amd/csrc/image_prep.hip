@@ -190,19 +190,6 @@ namespace {
 constexpr int kCvTW = 32, kCvTH = 16;           // output tile of resize_cubic_kernel
 constexpr int kCvRows = 4 * kCvTH;              // LDS rows of a tile: a contiguous span of source rows, or four rows per output row
 
-// a * b as an IEEE product of its own: under -ffp-contract=fast the backend fuses any multiply into the add that consumes it (a pragma does not
-// stop it), so the product passes through an empty asm statement, which the add cannot see through
-#ifdef PCDM_EMU
-#define PCDM_CV_OPAQUE(x) ((void)0)
-#else
-#define PCDM_CV_OPAQUE(x) asm volatile("" : "+v"(x))
-#endif
-__device__ __forceinline__ float cv_mul(float a, float b) {
-#pragma clang fp contract(off)
-    float p = a * b;
-    PCDM_CV_OPAQUE(p);
-    return p;
-}
 __device__ __forceinline__ void cv_cubic_coeffs(int d, double scale, int& s, float c[4]) {
 #pragma clang fp contract(off)
     double fd = ((double)d + 0.5) * scale;

@@ -1220,3 +1220,42 @@ def resize_cubic_f32(src: torch.Tensor, dst: torch.Tensor, index: int, *, nchw: 
                                                     N, Hd, Wd, int(index), int(bool(nchw)), float(divisor), _stream(src))
     _chk(_launch(src, call, "resize_cubic", 2.0 * 3 * Hd * Wd * 8 * 2, (src.shape[0], src.shape[1], Hd, Wd)), "pcdm_resize_cubic_f32")
     return dst
+
+
+# ------------------------------------------------------------------------------------ pose maps (pcdms_amd/pose.py is the public surface)
+POSE_TABLE_INTS = 740
+
+
+def pose_tables() -> list:
+    """The host-built constants of ``pose_draw``: {C, S} of every whole degree, then the 20 hand-edge colours (include/pcdm.h: pcdm_pose_tables)."""
+    buf = (C.c_int32 * POSE_TABLE_INTS)()
+    _chk(_lib.lib().pcdm_pose_tables(buf, POSE_TABLE_INTS), "pcdm_pose_tables")
+    return list(buf)
+
+
+def pose_ws_bytes(M: int, P: int) -> int:
+    """Workspace bytes of ``pose_draw``; -1: the library refuses the problem."""
+    return int(_lib.lib().pcdm_pose_ws_bytes(int(M), int(P)))
+
+
+def pose_draw(keypoints: torch.Tensor, scores: torch.Tensor, tables: torch.Tensor, out: torch.Tensor, ws: Optional[torch.Tensor], *, hands: bool,
+              faces: bool) -> torch.Tensor:
+    """keypoints fp32 [M, P, 134, 2], scores fp32 [M, P, 134] -> out uint8 [M, H, W, 3], the pose maps (include/pcdm.h: pcdm_pose_draw)."""
+    _c(keypoints, torch.float32); _c(scores, torch.float32); _c(tables, torch.int32); _c(out, torch.uint8)
+    M, P = int(keypoints.shape[0]), int(keypoints.shape[1])
+    assert tuple(keypoints.shape) == (M, P, 134, 2) and tuple(scores.shape) == (M, P, 134) and out.dim() == 4 and out.shape[0] == M and out.shape[3] == 3
+    assert tables.numel() == POSE_TABLE_INTS and keypoints.device == scores.device == tables.device == out.device
+    call = lambda: _lib.lib().pcdm_pose_draw(_ptr(keypoints), _ptr(scores), M, P, out.shape[1], out.shape[2], int(bool(hands)), int(bool(faces)),  # noqa: E731
+                                             _ptr(tables), _ptr(out), _ptr(ws), 0 if ws is None else ws.numel(), _stream(out))
+    _chk(_launch(out, call, "pose_draw", float(out.numel()), (M, P, out.shape[1], out.shape[2])), "pcdm_pose_draw")
+    return out
+
+
+def resize_linear_u8(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """src uint8 [M, Hs, Ws, 3] -> dst uint8 [M, Hd, Wd, 3]: OpenCV's 8-bit INTER_LINEAR (include/pcdm.h: pcdm_resize_linear_u8)."""
+    _c(src, torch.uint8); _c(dst, torch.uint8)
+    assert src.dim() == 4 and dst.dim() == 4 and src.shape[0] == dst.shape[0] and src.shape[3] == 3 and dst.shape[3] == 3 and src.device == dst.device
+    call = lambda: _lib.lib().pcdm_resize_linear_u8(_ptr(src), src.shape[0], src.shape[1], src.shape[2], _ptr(dst), dst.shape[1], dst.shape[2],  # noqa: E731
+                                                    _stream(src))
+    _chk(_launch(src, call, "resize_linear_u8", float(dst.numel()), tuple(src.shape[1:3]) + tuple(dst.shape[1:3])), "pcdm_resize_linear_u8")
+    return dst

@@ -9,6 +9,8 @@ on the host too: PIL resize / canvas pasting, ``CLIPImageProcessor``, PNG writin
 stay on the device as uint8, ``pcdms_amd.metrics.pick_best`` scores and selects there, and only the chosen image and the scores come back.
 With ``--preprocess_device gpu`` the input side moves as well: the decoded pixels of each image are uploaded once as uint8 and
 ``pcdms_amd.preprocess`` resizes, pastes, normalises and forms the CLIP pixels on the device -- the same bytes, so the same PNGs and best indices.
+With ``--pose_source keypoints`` the pose maps are not read as images: ``<pose name>.npz`` (keypoints, scores, size: tools/README.md) next to where
+the pose image would be is rendered on the device by ``pcdms_amd.pose.draw_pose`` -- the pixels tools/render_pose.py writes for that file.
 
 Differences, on purpose: ``--img_width`` is honoured (the reference parses it but reads ``args.img_weigh``); ``ImageProjModel_p``
 takes its sizes from the checkpoint / encoder config instead of the literals 1536 / 768 / 1024 (identical for the published
@@ -70,6 +72,18 @@ def pick_best_on_device(images: torch.Tensor, t_img: Image.Image, window=None):
     return Image.fromarray(image.cpu().numpy()), int(index.item()), [float(v) for v in scores.tolist()]
 
 
+def load_pose(path: str, source: str, device, on_device: bool):
+    """The pose map the driver reads at ``path``, not yet resized: decoded from the image file (``source`` "image") or rendered on ``device`` from
+    the keypoint file of the same name with the extension .npz ("keypoints").  A uint8 [h, w, 3] tensor on ``device`` (``on_device``) or a PIL image."""
+    if source == "keypoints":
+        with np.load(os.path.splitext(path)[0] + ".npz") as f:
+            kp, sc, (w, h) = torch.from_numpy(f["keypoints"].astype(np.float32)), torch.from_numpy(f["scores"].astype(np.float32)), (int(v) for v in f["size"])
+        pose = P.draw_pose(kp.to(device), sc.to(device), (h, w))[0]
+        return pose if on_device else Image.fromarray(pose.cpu().numpy())
+    img = Image.open(path).convert("RGB")
+    return torch.from_numpy(np.array(img)).to(device) if on_device else img
+
+
 def image_grid(imgs, rows, cols):
     w, h = imgs[0].size
     grid = Image.new("RGB", size=(cols * w, rows * h))
@@ -127,6 +141,7 @@ def inference(args, rank, select_test_datas):
 
     W, H = args.img_width, args.img_height
     pre_gpu = getattr(args, "preprocess_device", "host") == "gpu"
+    pose_source = getattr(args, "pose_source", "image")
     all_ssim = []
     start_time = time.time()
     split = args.json_path.split("/")[-1].split("_")[0]
@@ -137,13 +152,15 @@ def inference(args, rank, select_test_datas):
         t_pose_path = args.pose_path + data["target_image"].replace(".jpg", "_pose.jpg")
         t_img_dev = None
         load = lambda p: Image.open(p).convert("RGB").resize((W, H), Image.BICUBIC)  # noqa: E731
+        load_p = lambda p: load_pose(p, pose_source, device, False).resize((W, H), Image.BICUBIC)  # noqa: E731
         if pre_gpu:      # decode on the host, upload the raw pixels once per image, everything else on the device (pcdms_amd/preprocess.py)
             raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
-            vae_image, st_pose_t, s_img_u8 = P.stage2_inputs(raw(s_img_path), raw(s_pose_path), raw(t_pose_path), W, H)
+            vae_image, st_pose_t, s_img_u8 = P.stage2_inputs(raw(s_img_path), load_pose(s_pose_path, pose_source, device, True),
+                                                            load_pose(t_pose_path, pose_source, device, True), W, H)
             t_img_dev = P.resize(raw(t_img_path), (W, H))    # also what --metrics_device gpu scores against
             pix = P.clip_pixel_values(s_img_u8)
         else:
-            s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load(s_pose_path), load(t_pose_path)
+            s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load_p(s_pose_path), load_p(t_pose_path)
             s_img_t_mask = Image.new("RGB", (2 * W, H))          # [source | black]
             s_img_t_mask.paste(s_img, (0, 0))
             st_pose = Image.new("RGB", (2 * W, H))               # [source pose | target pose]
@@ -167,7 +184,7 @@ def inference(args, rank, select_test_datas):
         if pre_gpu and not on_device:      # the host scorer and the grid take PIL images: the device's bytes, brought back
             t_img = Image.fromarray(t_img_dev.cpu().numpy())
             if not args.calculate_metrics:   # (the grid's thumbnails; the pose halves are not kept as uint8 on the device)
-                s_img, s_pose, t_pose = Image.fromarray(s_img_u8.cpu().numpy()), load(s_pose_path), load(t_pose_path)
+                s_img, s_pose, t_pose = Image.fromarray(s_img_u8.cpu().numpy()), load_p(s_pose_path), load_p(t_pose_path)
         output = pipe(height=H, width=2 * W, guidance_rescale=0.0, vae_image=vae_image, s_img_proj_f=s_img_proj_f, st_pose_f=st_pose_f,
                       pred_t_img_embed=pred_t_img_embed, num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
                       num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
@@ -231,6 +248,9 @@ def build_parser():
     p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
                    help="where the inputs are resized, pasted, normalised and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the "
                         "reference) or gpu (pcdms_amd.preprocess, the same bytes)")
+    p.add_argument("--pose_source", choices=("image", "keypoints"), default="image",
+                   help="where the pose maps come from: image (the pose image files, as the reference) or keypoints (<pose name>.npz next to them, "
+                        "rendered on the device by pcdms_amd.pose)")
     p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p
