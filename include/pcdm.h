@@ -214,6 +214,11 @@ int pcdm_flash_attn_thr(const void* q, int64_t ldq, const void* k, int64_t ldk, 
  *      scales; twice the bf16 matrix rate).  No reference counterpart (attention enters at stage2_batchtest_inpaint_model.py:133).
  * pcdm_quantize_fp8: y[r, c] = e4m3(sat(x[r, c] * scale)) for bf16 x [rows, ldx] -> bytes y [rows, ldy]; columns [cols, cols_pad) are
  *   written as zero (cols_pad % 8 == 0).  Used for K [B*Lk, C] and V^T [B*C, Lk -> padded to a multiple of 16].
+ *   sat clamps to +-448 (+-inf included) and keeps NaN: a NaN in x gives an e4m3 NaN byte (0x7f or 0xff), never a finite number.
+ *   x needs only its natural 2-byte alignment and any ldx >= cols: rows are read 16 bytes at a time where x is 16-byte aligned and
+ *   ldx % 8 == 0, element by element otherwise (the same bytes come out).  y is stored in 8-byte pieces: y 8-byte aligned, ldy % 8 == 0.
+ *   Returns -1 without launching (y untouched) for: a NULL pointer; rows or cols < 1; cols_pad < cols or not a multiple of 8; ldy < cols_pad
+ *   or not a multiple of 8; ldx < cols; y not 8-byte aligned.
  * pcdm_flash_attn_fp8: q bf16 as in pcdm_flash_attn; k8 [B*Lk, ldk] / vt8 [B, H*64, ldvt] e4m3 bytes (ldk, ldvt multiples of 16,
  *   ldvt >= Lk, padding zero); k_descale / v_descale undo the quantisation scales; thr_log2 <= 8.  fp32 softmax, P rounded to e4m3.
  *   V^T padding: as for pcdm_flash_attn the columns [Lk, ldvt) inside the last key tile are multiplied by an exact zero; pcdm_quantize_fp8
@@ -263,7 +268,8 @@ int pcdm_time_class_combine(const float* emb_t, const float* cls, void* out_bf16
  * mask == NULL: the 8-channel stage-3 input cat([latents, gen_t_img_latents], 1) (stage3_refined_pipeline.py:538). */
 int pcdm_assemble_input(const float* latents, int N, int rep, const float* mask, int mask_b, const float* masked,
                         int masked_b, void* out, int h, int w, int cpad, pcdm_stream_t s);
-/* NCHW fp32 -> NHWC bf16 (pose feature st_pose_f, ref :430-431) and back. */
+/* NCHW fp32 -> NHWC bf16 (pose feature st_pose_f, ref :430-431) and back.  y 16-byte aligned for the first (8-channel stores).  Both return -1
+ * without launching for a NULL pointer or B, C or HW < 1; the first also for Cpad < C or Cpad % 8 != 0. */
 int pcdm_nchw_f32_to_nhwc_bf16(const float* x, void* y, int B, int C, int Cpad, int HW, pcdm_stream_t s); /* y [B,HW,Cpad], c >= C zero */
 int pcdm_nhwc_bf16_to_nchw_f32(const void* x, float* y, int B, int C, int HW, pcdm_stream_t s);
 int pcdm_f32_to_bf16(const float* x, void* y, int64_t n, pcdm_stream_t s);
@@ -306,7 +312,11 @@ int pcdm_unclip_step_dev(const float* pred, int cfg, float g, float* x, const fl
 int pcdm_rescale_noise_cfg(const float* cfg_eps, const float* text_eps, float* out, int N, int64_t n,
                            float guidance_rescale, pcdm_stream_t s);
 /* p[r, c] = softmax_c(scale * s[r, c]) : fp32 [rows, ld_s] -> bf16 [rows, ld_p], cols <= 8192.  The VAE's single-head
- * d = 512 attention (AutoencoderKL mid block) = pcdm_gemm (K Q^T, fp32) + this + pcdm_gemm (P V). */
+ * d = 512 attention (AutoencoderKL mid block) = pcdm_gemm (K Q^T, fp32) + this + pcdm_gemm (P V).
+ * Columns [cols, ld_p) of p are not written.  Domain: every score finite or -inf (which gives exactly 0), |scale * s * log2(e)| < 1e30
+ * for the finite ones, and at least one finite score per row; a row of only -inf gives NaN, as torch.softmax does.  Outside that
+ * domain (a row below -1e30 throughout, a product that overflows fp32) the row may come out NaN where the exact softmax exists.
+ * Returns -1 without launching (p untouched) for: a NULL pointer; rows or cols < 1; cols > 8192; ld_s < cols; ld_p < cols. */
 int pcdm_softmax_rows(const float* s_in, void* p_out, int rows, int cols, int64_t ld_s, int64_t ld_p, float scale,
                       pcdm_stream_t s);
 /* AutoencoderKL helpers (stage2_inpaint_pipeline.py:443-444, :528-532):

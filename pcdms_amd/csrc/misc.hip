@@ -443,7 +443,7 @@ extern "C" int pcdm_assemble_input(const float* latents, int N, int rep, const f
 }
 
 extern "C" int pcdm_nchw_f32_to_nhwc_bf16(const float* x, void* y, int B, int C, int Cpad, int HW, pcdm_stream_t s) {
-    if (!x || !y || Cpad % 8 || Cpad < C) return -1;
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || Cpad % 8 || Cpad < C) return -1;
     const int64_t total = (int64_t)B * HW * (Cpad / 8);
     PCDM_LAUNCH(nchw_to_nhwc_kernel, grid1d(total, 256), dim3(256), 0, (hipStream_t)s, x, (u16*)y, C, Cpad, HW, total);
     PCDM_CHECK_LAUNCH();
@@ -451,7 +451,7 @@ extern "C" int pcdm_nchw_f32_to_nhwc_bf16(const float* x, void* y, int B, int C,
 }
 
 extern "C" int pcdm_nhwc_bf16_to_nchw_f32(const void* x, float* y, int B, int C, int HW, pcdm_stream_t s) {
-    if (!x || !y) return -1;
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0) return -1;
     const int64_t total = (int64_t)B * HW * C;
     PCDM_LAUNCH(nhwc_to_nchw_kernel, grid1d(total, 256), dim3(256), 0, (hipStream_t)s, (const u16*)x, y, C, HW, total);
     PCDM_CHECK_LAUNCH();
@@ -528,8 +528,9 @@ extern "C" int pcdm_rescale_noise_cfg(const float* cfg_eps, const float* text_ep
     return 0;
 }
 
-// bf16 [rows, ldx] -> e4m3 [rows, ldy] (bytes), y = sat(x * scale); 8 elements per thread (16 B in, 8 B out); columns >= cols of a row
-// (up to cols_pad) are written as zero: the K / V^T operands of pcdm_flash_attn_fp8
+// bf16 [rows, ldx] -> e4m3 [rows, ldy] (bytes), y = sat(x * scale); 8 elements per thread (16 B in where x and ldx keep every row 16-byte
+// aligned, eight 2-byte loads otherwise; 8 B out); columns >= cols of a row (up to cols_pad) are written as zero: the K / V^T operands of
+// pcdm_flash_attn_fp8
 __global__ __launch_bounds__(256) void quantize_fp8_kernel(const u16* __restrict__ x, uint8_t* __restrict__ y, int64_t rows, int cols,
                                                            int cols_pad, int64_t ldx, int64_t ldy, float scale) {
     const int per_row = cols_pad / 8;
@@ -538,7 +539,7 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const u16* __restrict
     const int64_t r = i / per_row;
     const int c = (int)(i - r * per_row) * 8;
     float v[8];
-    if (c + 8 <= cols && (ldx & 7) == 0) {   // (rows start 16-byte aligned)
+    if (c + 8 <= cols && (ldx & 7) == 0 && ((uintptr_t)x & 15) == 0) {   // (every row starts 16-byte aligned: base and row stride)
         const u16x8 a = *(const u16x8*)(x + r * ldx + c);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = bf2f(a[e]);
@@ -547,14 +548,18 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const u16* __restrict
         for (int e = 0; e < 8; ++e) v[e] = c + e < cols ? bf2f(x[r * ldx + c + e]) : 0.f;
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = fminf(fmaxf(v[e] * scale, -448.f), 448.f);
+    for (int e = 0; e < 8; ++e) {   // saturate; comparisons, not fminf / fmaxf: those drop a NaN operand, and a NaN must reach the convert (-> 0x7f / 0xff)
+        const float t = v[e] * scale;
+        v[e] = t > 448.f ? 448.f : (t < -448.f ? -448.f : t);
+    }
     u32x2 o = {pack4_fp8(v[0], v[1], v[2], v[3]), pack4_fp8(v[4], v[5], v[6], v[7])};
     *(u32x2*)(y + r * ldy + c) = o;
 }
 
 extern "C" int pcdm_quantize_fp8(const void* x, void* y, int64_t rows, int cols, int cols_pad, int64_t ldx, int64_t ldy, float scale,
                                  pcdm_stream_t s) {
-    if (!x || !y || rows <= 0 || cols <= 0 || cols_pad < cols || cols_pad % 8 || ldy % 8 || ldy < cols_pad || ldx < cols) return -1;
+    if (!x || !y || rows <= 0 || cols <= 0 || cols_pad < cols || cols_pad % 8 || ldy % 8 || ldy < cols_pad || ldx < cols ||
+        ((uintptr_t)y & 7)) return -1;   // (y is stored in 8-byte pieces)
     const int64_t total = rows * (cols_pad / 8);
     PCDM_LAUNCH(quantize_fp8_kernel, grid1d(total, 256), dim3(256), 0, (hipStream_t)s, (const u16*)x, (uint8_t*)y, rows, cols, cols_pad,
                 ldx, ldy, scale);
@@ -564,7 +569,7 @@ extern "C" int pcdm_quantize_fp8(const void* x, void* y, int64_t rows, int cols,
 
 extern "C" int pcdm_softmax_rows(const float* s_in, void* p_out, int rows, int cols, int64_t ld_s, int64_t ld_p, float scale,
                                  pcdm_stream_t s) {
-    if (!s_in || !p_out || rows <= 0 || cols <= 0 || cols > 8192) return -1;
+    if (!s_in || !p_out || rows <= 0 || cols <= 0 || cols > 8192 || ld_s < cols || ld_p < cols) return -1;
     PCDM_LAUNCH(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)s, s_in, (u16*)p_out, cols, ld_s, ld_p,
                 scale * 1.44269504088896341f);
     PCDM_CHECK_LAUNCH();

@@ -60,7 +60,7 @@ def test_vae_softmax_rows_and_helpers(backend):
     u8 = torch.empty(B, 8, 8, 3, dtype=torch.uint8, device=dev)
     ops._chk(_lib.lib().pcdm_image_to_uint8(img.data_ptr(), u8.data_ptr(), B, 4, 64, ops._stream(img)), "u8")
     backend.sync()
-    assert (u8.cpu().int() - O.postprocess_uint8(img.cpu()[:, :3]).int()).abs().max() <= 1
+    assert torch.equal(u8.cpu(), O.postprocess_uint8(img.cpu()[:, :3]))   # (bit for bit: tests/test_small_ops_conformance.py sweeps the rounding edges)
 
 
 def test_vae_tiny_encode_decode(backend):
