@@ -334,6 +334,7 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         if self._w is None:
             self._pack()
         W, cfg, dev = self._w, self.config, self._device
+        taps = getattr(self, "_taps", None)   # test hook (see _forward_nhwc)
         boc = self._boc
         temb_dim = boc[0] * 4
         ehs = encoder_hidden_states
@@ -365,6 +366,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                 for b in range(B):
                     ops.nchw_to_nhwc_bf16(pose, buf[b:b + 1])
             cond.pose_nhwc = buf
+        if taps is not None:
+            taps.update({k: v.clone() for k, v in (("cls_emb", cond.cls_emb), ("pose_nhwc", cond.pose_nhwc)) if v is not None})
         e32 = ehs.to(dev, torch.float32).contiguous()
         if zero_ctx_batches is None:   # leading all-zero batch entries (bare callers; the pipelines know and say so)
             nz = (e32.reshape(B, -1) != 0).any(dim=1).to(torch.int32)
@@ -382,6 +385,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             kbuf = self._buf(("k2", p), (Bc * L, c))
             vtbuf = self._buf(("vt2", p), (Bc, c, Lp), zero=True)
             ops.gemm(ctx, W[p]["kv2"], kbuf, rows_per_batch=L, epilogue=ops.EPI_SPLIT_VT, out2=vtbuf, vt_col0=c)
+            if taps is not None:
+                taps[p + "k2"], taps[p + "vt2"] = kbuf.clone(), vtbuf.clone()
             if self._attn_fp8:   # e4m3 copies, once per call
                 L16 = (L + 15) // 16 * 16
                 k8 = ops.quantize_fp8(kbuf, self._buf(("k2_8", p), (Bc * L, c), ops.FP8))
@@ -389,6 +394,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                 cond.kv[p] = (k8, vt8.view(Bc, c, L16))
             else:
                 cond.kv[p] = (kbuf, vtbuf)
+        if taps is not None:
+            taps["ctx"] = ctx.clone()
         if timesteps is not None and TIME_TABLE:
             self._time_table(cond, timesteps)
         return cond
@@ -501,7 +508,24 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
 
     # -- the schedule proper; x_in is NHWC bf16 [B,h,w,cin_pad]; returns fp32 NCHW eps (a reused buffer)
     def _forward_nhwc(self, x_in, B, h, w, timestep, cond: Conditioning, step_dev=None) -> torch.Tensor:
-        taps = getattr(self, "_taps", None)   # test hook: a dict set by a parity test receives the residual stream [B*HW, C] bf16 at the block boundaries
+        # test hook: a dict set by a parity test receives a clone of every tensor a later kernel reads (tests/test_schedule_conformance.py; the
+        # residual stream [B*HW, C] bf16 at the block boundaries: tests/test_fullsize_parity.py).  None (always, outside those tests): nothing is cloned
+        taps = getattr(self, "_taps", None)
+        pend: List[Tuple[str, Any]] = []
+
+        def tap(name, t):
+            """Record ``t``; a deferred split-K tensor has no bf16 value yet: it is recorded by ``tap_stored`` after the GroupNorm that writes
+            it -- if that norm stores it at all (where it does not, the stage boundary is the norm's output)."""
+            if isinstance(t, ops.DeferredGemm):
+                if t.store:
+                    pend.append((name, t))
+            else:
+                taps[name] = t.clone()
+
+        def tap_stored():
+            while pend:
+                name, t = pend.pop()
+                taps[name] = t.out.clone()
         W, cfg, dev = self._w, self.config, self._device
         boc, G, eps = self._boc, cfg.norm_num_groups, cfg.norm_eps
         nlev = len(boc)
@@ -538,6 +562,10 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             emb_bf = ops.f32_to_bf16(emb_act, self._buf("emb_bf", (B, temb_dim)))
             temb = ops.gemm(emb_bf, W["temb"], self._buf("temb", (B, W["temb_n"]), torch.float32), rows_per_batch=1,
                             epilogue=ops.EPI_NCHW_F32)                      # fp32 [B, 20160] (rows_per_batch = 1: "NCHW" == row-major)
+            if taps is not None:
+                tap("t_emb", t_emb), tap("emb_act", emb_act), tap("emb_bf", emb_bf), tap("temb", temb)
+        if taps is not None:
+            tap("x_in", x_in)
 
         # Split-K convolutions (levels 1-3: M <= 11264 rows against K up to 23040) leave their fp32 partial slabs for the GroupNorm that
         # always follows -- conv1 -> norm2, conv2 / down- / upsampling conv -> the next block's first norm -- which reduces them while it
@@ -562,16 +590,27 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                 cv = dict(B=B, Hi=hh, Wi=ww, Ho=hh, Wo=ww)
                 h1 = ops.gemm(n1, r["conv1"], self._buf("c1", (M, cout)), conv=cv, rowvec=tv, rows_per_batch=HW_, defer_reduce=False,
                               rowvec_step=rv_step, rowvec_step_stride=rv_stride, rowvec_step_count=rv_count, step_error=rv_err)
+            if taps is not None:
+                tap_stored()
+                tap(p + "n1", n1), tap(p + "h1", h1)   # (h1: not where it stays in the split-K workspace for norm2)
             n2 = ops.groupnorm(h1, None, B, HW_, G, eps, r["n2"][0], r["n2"][1], True, self._buf("gn", (M, cout)), ws)
+            if taps is not None:
+                tap(p + "n2", n2)
             if "conv2s" in r:   # conv2 + conv_shortcut as one contraction: the block's input enters through the extra K (FUSE_SHORTCUT above)
-                return ops.gemm(n2, r["conv2s"], self._buf(name, (M, cout)), conv=cv, a2=x1, a3=x2, defer_reduce=True if gn_next else None,
-                                rows_per_batch=HW_)
-            if "short" in r:
-                res = ops.gemm(x1, r["short"], self._buf("sc", (M, cout)), a2=x2)
+                o = ops.gemm(n2, r["conv2s"], self._buf(name, (M, cout)), conv=cv, a2=x1, a3=x2, defer_reduce=True if gn_next else None,
+                             rows_per_batch=HW_)
             else:
-                res = x1
-            return ops.gemm(n2, r["conv2"], self._buf(name, (M, cout)), conv=cv, residual=res, res_mod=M,
-                            defer_reduce=True if gn_next else None, rows_per_batch=HW_)
+                if "short" in r:
+                    res = ops.gemm(x1, r["short"], self._buf("sc", (M, cout)), a2=x2)
+                    if taps is not None:
+                        tap(p + "sc", res)
+                else:
+                    res = x1
+                o = ops.gemm(n2, r["conv2"], self._buf(name, (M, cout)), conv=cv, residual=res, res_mod=M,
+                             defer_reduce=True if gn_next else None, rows_per_batch=HW_)
+            if taps is not None:
+                tap(p + "out", o)
+            return o
 
         def transformer(p, x, HW_, name):
             a = W[p]
@@ -579,6 +618,9 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             ws = self._buf("gnws", (int(ops._lib.lib().pcdm_groupnorm_ws_floats(B, 4096)),), torch.float32, zero=True)
             n0 = ops.groupnorm(x, None, B, HW_, G, 1e-6, a["norm"][0], a["norm"][1], False, self._buf("gn", (M, c)), ws)
             x = ops.as_tensor(x)
+            if taps is not None:
+                tap_stored()
+                tap(p + "n0", n0)
             # Row statistics travel with the rows (round 5, levels 1-3): the linear that writes the input of a LayerNorm -- proj_in, attn1.to_out +
             # residual, attn2.to_out + residual -- also writes the {sum, M2} of every 32-column run (`row_stats`), and the LayerNorm-folded
             # projection that reads the rows next merges them: no LayerNorm launch, no statistics work in that GEMM's loop (ops._gemm_ln)
@@ -600,6 +642,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                 at = ops.flash_attn_fp8(qk[:, :c], k8, vt8.view(B, c, HW16), self._buf("at", (M, c)), B, H, HW_, HW_)
             else:
                 at = ops.flash_attn(qk[:, :c], qk[:, c:], vt, self._buf("at", (M, c)), B, H, HW_, HW_)
+            if taps is not None:
+                tap(p + "t0", t0), tap(p + "qk", qk), tap(p + "vt", vt), tap(p + "at", at)
             t1 = ops.gemm(at, a["o1"], self._buf("t1", (M, c)), residual=t0, res_mod=M, row_stats=want(a.get("q2_ln"), M - r0, ops.EPI_STORE))
             # cross-attention over the context tokens; the first n0 batch entries have an all-zero context, for which
             # attn2(x) == to_out.0.bias exactly: their rows skip LN2 / to_q / attention and enter
@@ -609,15 +653,25 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             q2 = ops.gemm(t1[r0:], a["q2"], self._buf("q2", (M, c))[r0:], ln=(a["ln2"][0], a["ln2"][1], 1e-5),
                           ln_buf=self._buf("ln", (M, c))[r0:], pw_ln=a.get("q2_ln"), row_stats=None if rs is None else rs[r0:])
             (ops.flash_attn_fp8 if self._attn_fp8 else ops.flash_attn)(q2, k2, vt2, at2[r0:], B - nzero, H, HW_, L)
+            if taps is not None:   # (q2 / at2: the rows behind the zero-context entries only)
+                tap(p + "t1", t1), tap(p + "q2", q2), tap(p + "at2", at2[r0:])
             t2 = ops.gemm(at2, a["o2"], self._buf("t0", (M, c)), residual=t1, res_mod=M, zero_rows=r0,
                           row_stats=want(a.get("ff1_ln"), M, ops.EPI_GEGLU))
             # GEGLU feed-forward
             ff = ops.gemm(t2, a["ff1"], self._buf("ff", (M, 4 * c)), epilogue=ops.EPI_GEGLU, ln=(a["ln3"][0], a["ln3"][1], 1e-5),
                           ln_buf=self._buf("ln", (M, c)), pw_ln=a.get("ff1_ln"), row_stats=rs)
+            if taps is not None:
+                tap(p + "t2", t2), tap(p + "ff", ff)
             if "ffo" in a:   # ff.net.2 + residual and proj_out + residual as one contraction over [ff | t2] (FUSE_FF_OUT above)
-                return ops.gemm(ff, a["ffo"], self._buf(name, (M, c)), a2=t2, residual=x, res_mod=M)
-            t3 = ops.gemm(ff, a["ff2"], self._buf("t1", (M, c)), residual=t2, res_mod=M)
-            return ops.gemm(t3, a["proj_out"], self._buf(name, (M, c)), residual=x, res_mod=M)
+                o = ops.gemm(ff, a["ffo"], self._buf(name, (M, c)), a2=t2, residual=x, res_mod=M)
+            else:
+                t3 = ops.gemm(ff, a["ff2"], self._buf("t1", (M, c)), residual=t2, res_mod=M)
+                o = ops.gemm(t3, a["proj_out"], self._buf(name, (M, c)), residual=x, res_mod=M)
+                if taps is not None:
+                    tap(p + "t3", t3)
+            if taps is not None:
+                tap(p + "out", o)
+            return o
 
         # ---- 2. conv_in + pose (ref :742)
         HW = h * w
@@ -631,6 +685,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             x = ops.gemm(x_in, W["conv_in"], self._buf("skip0", (B * HW, boc[0])), conv=dict(B=B, Hi=h, Wi=w, Ho=h, Wo=w),
                          residual=None if pose_nhwc is None else pose_nhwc.view(-1, boc[0]),
                          res_mod=0 if pose_nhwc is None else pose_nhwc.shape[0] * HW)
+        if taps is not None:
+            tap("conv_in.out", x)
         # ---- 3. down (ref :746-761)
         skips: List[Tuple[torch.Tensor, int, int]] = [(x, h, w)]
         hh, ww = h, w
@@ -653,6 +709,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                 x = ops.gemm(x.view(B, hh, ww, boc[i]), W[f"down_blocks.{i}.downsamplers.0.conv."],
                              self._buf(f"ds{i}", (B * ho * wo, boc[i])),
                              conv=dict(B=B, Hi=hh, Wi=ww, Ho=ho, Wo=wo, stride=2), defer_reduce=True)   # -> the next block's norm1
+                if taps is not None:
+                    tap(f"down_blocks.{i}.downsamplers.0.out", x)
                 hh, ww = ho, wo
                 skips.append((skip_of(x), hh, ww))
         all_skips = list(skips) if taps is not None else None
@@ -681,11 +739,15 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                     ph = ops.gemm(x.view(B, hh, ww, rev[i]), w4, self._buf("usp", (B * hh * ww, 4 * rev[i])),
                                   conv=dict(B=B, Hi=hh, Wi=ww, Ho=hh, Wo=ww), tap_lut=ops.UPSAMPLE_TAP_LUT, tap_group_n=rev[i])
                     x = ops.pixel_shuffle2(ph, self._buf("us", (B * ho * wo, rev[i])), B, hh, ww, rev[i])
+                    if taps is not None:
+                        tap(f"up_blocks.{i}.upsamplers.0.ph", ph), tap(f"up_blocks.{i}.upsamplers.0.out", x)
                     hh, ww = ho, wo
                     continue
                 x = ops.gemm(x.view(B, hh, ww, rev[i]), W[f"up_blocks.{i}.upsamplers.0.conv."],
                              self._buf("us", (B * ho * wo, rev[i])),
                              conv=dict(B=B, Hi=hh, Wi=ww, Ho=ho, Wo=wo, upsample=1), defer_reduce=True)    # -> the next block's norm1
+                if taps is not None:
+                    tap(f"up_blocks.{i}.upsamplers.0.out", x)
                 hh, ww = ho, wo
         # ---- 6. post-process (ref :817-820)
         ws = self._buf("gnws", (int(ops._lib.lib().pcdm_groupnorm_ws_floats(B, 4096)),), torch.float32, zero=True)
@@ -694,6 +756,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         ops.gemm(n, W["conv_out"], out, conv=dict(B=B, Hi=h, Wi=w, Ho=h, Wo=w), rows_per_batch=HW,
                  epilogue=ops.EPI_NCHW_F32)
         if taps is not None:
+            tap_stored()
+            tap("norm_out", n), tap("eps", out)
             # the down-path skip tensors, read back AFTER the forward: a deferred split-K tensor's buffer is filled by the norm that
             # consumes it, and every skip buffer stays untouched until here.  Names as oracle.unet.unet_forward's taps.
             names = ["conv_in"]

@@ -161,34 +161,45 @@ class AutoencoderKL(HipModel):
         self._w = w
 
     # ---------------------------------------------------------------- blocks
-    def _gn(self, x, B, HW, gb, silu, name):
+    def _tap(self, name, t):
+        """Test hook (tests/test_schedule_conformance.py): with ``self._taps`` set to a dict, a clone of every tensor a later kernel reads is
+        recorded under the state-dict prefix of the layer that wrote it.  ``None`` (always, outside that test): nothing is cloned."""
+        taps = getattr(self, "_taps", None)
+        if taps is not None:
+            taps[name] = t.clone()
+        return t
+
+    def _gn(self, x, B, HW, gb, silu, name, tag=""):
         C = x.shape[-1]
         ws = self._buf("gnws", (int(_lib.lib().pcdm_groupnorm_ws_floats(B, C)),), torch.float32, zero=True)
-        return ops.groupnorm(x, None, B, HW, self.config.norm_num_groups, 1e-6, gb[0], gb[1], silu,
-                             self._buf(name, (B * HW, C)), ws)
+        return self._tap(tag, ops.groupnorm(x, None, B, HW, self.config.norm_num_groups, 1e-6, gb[0], gb[1], silu,
+                                            self._buf(name, (B * HW, C)), ws))
 
-    def _resnet(self, r, x, B, H, W, name):
+    def _resnet(self, r, x, B, H, W, name, tag=""):
         HW, M = H * W, B * H * W
         cout = r["conv1"].N
         cv = dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W)
-        n1 = self._gn(x, B, HW, r["n1"], True, "gn")
-        h1 = ops.gemm(n1, r["conv1"], self._buf("c1", (M, cout)), conv=cv)
-        n2 = self._gn(h1, B, HW, r["n2"], True, "gn2")
-        resid = ops.gemm(x, r["short"], self._buf("sc", (M, cout))) if "short" in r else x
-        return ops.gemm(n2, r["conv2"], self._buf(name, (M, cout)), conv=cv, residual=resid, res_mod=M)
+        n1 = self._gn(x, B, HW, r["n1"], True, "gn", tag + "n1")
+        h1 = self._tap(tag + "h1", ops.gemm(n1, r["conv1"], self._buf("c1", (M, cout)), conv=cv))
+        n2 = self._gn(h1, B, HW, r["n2"], True, "gn2", tag + "n2")
+        resid = self._tap(tag + "sc", ops.gemm(x, r["short"], self._buf("sc", (M, cout)))) if "short" in r else x
+        return self._tap(tag + "out", ops.gemm(n2, r["conv2"], self._buf(name, (M, cout)), conv=cv, residual=resid, res_mod=M))
 
-    def _mid(self, m, x, B, H, W):
+    def _mid(self, m, x, B, H, W, tag=""):
         """resnet -> single-head attention (d = C) with residual -> resnet."""
         HW, M, C = H * W, B * H * W, m["c"]
-        x = self._resnet(m["r0"], x, B, H, W, "ma")
-        n = self._gn(x, B, HW, m["gn"], False, "gn")
+        x = self._resnet(m["r0"], x, B, H, W, "ma", tag + "resnets.0.")
+        n = self._gn(x, B, HW, m["gn"], False, "gn", tag + "attentions.0.n")
         qk = self._buf("qk", (M, 2 * C))
         vt = self._buf("vt", (B, C, (HW + 7) // 8 * 8), zero=True)   # key pitch padded to 16 bytes
         ops.gemm(n, m["qkv"], qk, rows_per_batch=HW, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * C)
         # o = softmax(q k^T / sqrt(C)) v for the whole batch in one launch: no HW x HW scores anywhere
         at = ops.attn_wide(qk[:, :C], qk[:, C:], vt, self._buf("at", (M, C)), B, HW, HW, C ** -0.5)
         y = ops.gemm(at, m["out"], self._buf("mb", (M, C)), residual=x, res_mod=M)
-        return self._resnet(m["r1"], y, B, H, W, "mc")
+        if getattr(self, "_taps", None) is not None:
+            for k, v in (("qk", qk), ("vt", vt), ("at", at), ("out", y)):
+                self._tap(tag + "attentions.0." + k, v)
+        return self._resnet(m["r1"], y, B, H, W, "mc", tag + "resnets.1.")
 
     # ---------------------------------------------------------------- encode / decode
     @torch.no_grad()
@@ -203,18 +214,21 @@ class AutoencoderKL(HipModel):
         boc, L = cfg.block_out_channels, cfg.layers_per_block
         xin = ops.nchw_to_nhwc_bf16(x.to(self._device), self._buf("e.in", (B, H, W, 64)), cpad=64)
         h = ops.gemm(xin, W_["e.conv_in"], self._buf("e.x0", (B * H * W, boc[0])), conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W))
+        self._tap("encoder.in", xin), self._tap("encoder.conv_in.out", h)
         for i in range(len(boc)):
             for j in range(L):
-                h = self._resnet(W_[f"e.d{i}.r{j}"], h, B, H, W, "ra" if j % 2 == 0 else "rb")
+                h = self._resnet(W_[f"e.d{i}.r{j}"], h, B, H, W, "ra" if j % 2 == 0 else "rb", f"encoder.down_blocks.{i}.resnets.{j}.")
             if i != len(boc) - 1:   # Downsample2D(padding=0): zero pad bottom/right only
                 h = ops.gemm(h, W_[f"e.d{i}.ds"], self._buf("ds", (B * (H // 2) * (W // 2), boc[i])),
                              conv=dict(B=B, Hi=H, Wi=W, Ho=H // 2, Wo=W // 2, stride=2, no_pad_lo=1))
+                self._tap(f"encoder.down_blocks.{i}.downsamplers.0.out", h)
                 H, W = H // 2, W // 2
-        h = self._mid(W_["e.mid"], h, B, H, W)
-        n = self._gn(h, B, H * W, W_["e.norm_out"], True, "gn")
+        h = self._mid(W_["e.mid"], h, B, H, W, "encoder.mid_block.")
+        n = self._gn(h, B, H * W, W_["e.norm_out"], True, "gn", "encoder.norm_out")
         mom = torch.empty(B, 2 * cfg.latent_channels, H, W, dtype=torch.float32, device=self._device)
         ops.gemm(n, W_["e.conv_out"], mom, conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W), rows_per_batch=H * W,
                  epilogue=ops.EPI_NCHW_F32)
+        self._tap("moments", mom)
         dist = DiagonalGaussianDistribution(mom)
         return AutoencoderKLOutput(dist) if return_dict else (dist,)
 
@@ -235,23 +249,27 @@ class AutoencoderKL(HipModel):
         zin = ops.nchw_to_nhwc_bf16(z.to(self._device), self._buf("d.in", (B, H, W, 64)), cpad=64)
         zq = ops.gemm(zin.view(B * H * W, 64), W_["d.post_quant"], self._buf("d.zq", (B * H * W, 64), zero=True))
         h = ops.gemm(zq, W_["d.conv_in"], self._buf("d.x0", (B * H * W, rev[0])), conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W))
-        h = self._mid(W_["d.mid"], h, B, H, W)
+        self._tap("decoder.in", zin), self._tap("zq", zq), self._tap("decoder.conv_in.out", h)
+        h = self._mid(W_["d.mid"], h, B, H, W, "decoder.mid_block.")
         for i in range(len(boc)):
             for j in range(L + 1):
-                h = self._resnet(W_[f"d.u{i}.r{j}"], h, B, H, W, "ra" if j % 2 == 0 else "rb")
+                h = self._resnet(W_[f"d.u{i}.r{j}"], h, B, H, W, "ra" if j % 2 == 0 else "rb", f"decoder.up_blocks.{i}.resnets.{j}.")
             if i != len(boc) - 1:
                 if f"d.u{i}.us4" in W_:   # Upsample2D as four 2x2 phase kernels on the low-res tensor (one launch, N = 4 C) + a pixel shuffle
                     ph = ops.gemm(h, W_[f"d.u{i}.us4"], self._buf("usp", (B * H * W, 4 * rev[i])), conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W),
                                   tap_lut=ops.UPSAMPLE_TAP_LUT, tap_group_n=rev[i])
+                    self._tap(f"decoder.up_blocks.{i}.upsamplers.0.ph", ph)
                     h = ops.pixel_shuffle2(ph, self._buf("us", (B * 4 * H * W, rev[i])), B, H, W, rev[i])
                 else:               # nearest x2 folded into the conv's gather
                     h = ops.gemm(h, W_[f"d.u{i}.us"], self._buf("us", (B * 4 * H * W, rev[i])),
                                  conv=dict(B=B, Hi=H, Wi=W, Ho=2 * H, Wo=2 * W, upsample=1))
+                self._tap(f"decoder.up_blocks.{i}.upsamplers.0.out", h)
                 H, W = 2 * H, 2 * W
-        n = self._gn(h, B, H * W, W_["d.norm_out"], True, "gn")
+        n = self._gn(h, B, H * W, W_["d.norm_out"], True, "gn", "decoder.norm_out")
         img4 = self._buf("img4", (B, 4, H, W), torch.float32)      # 3 channels + 1 padding channel
         ops.gemm(n, W_["d.conv_out"], img4, conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W), rows_per_batch=H * W,
                  epilogue=ops.EPI_NCHW_F32)
+        self._tap("img4", img4)
         return img4
 
     @torch.no_grad()
