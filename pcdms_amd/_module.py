@@ -183,6 +183,14 @@ class HipModel:
         if self._device.type != "cuda" and not _lib.is_emulator():
             raise RuntimeError(f"{type(self).__name__} runs on the MI355X only: call .to('cuda') (there is no CPU implementation)")
 
+    def _tap(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        """Test hook (tests/test_cond_stack_conformance.py): with ``self._taps`` set to a dict, a clone of ``t`` -- a tensor a later launch
+        reads -- is recorded under ``name``.  ``None`` (always, outside that test): nothing is cloned, nothing is launched."""
+        taps = getattr(self, "_taps", None)
+        if taps is not None:
+            taps[name] = t.clone()
+        return t
+
     def _buf(self, name: str, shape, dtype=BF16, zero: bool = False) -> torch.Tensor:
         key = (name, tuple(shape), dtype)
         t = self._bufs.get(key)

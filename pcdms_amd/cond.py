@@ -60,18 +60,21 @@ class ControlNetConditioningEmbedding(HipModel):
         down = 2 ** (len(self.boc) - 1)
         if Cc != self.cond_channels or H % down or W % down:
             raise ValueError(f"conditioning must be [B,{self.cond_channels},H,W] with H, W multiples of {down}")
-        x = ops.nchw_to_nhwc_bf16(conditioning.to(self._device), self._buf("in", (B, H, W, 64)), cpad=64)
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
+        x = tap("in", ops.nchw_to_nhwc_bf16(conditioning.to(self._device), self._buf("in", (B, H, W, 64)), cpad=64))
         h = ops.gemm(x, w["conv_in"], self._buf("x0", (B * H * W, w["conv_in"].Npad)), conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W),
                      act=ops.ACT_SILU)
+        tap("conv_in", h)
         for i, pw in enumerate(w["blocks"]):
             s = 2 if i % 2 else 1
             Ho, Wo = H // s, W // s
             h = ops.gemm(h, pw, self._buf(f"b{i}", (B * Ho * Wo, pw.Npad)), conv=dict(B=B, Hi=H, Wi=W, Ho=Ho, Wo=Wo, stride=s),
                          act=ops.ACT_SILU)
+            tap(f"blocks.{i}", h)
             H, W = Ho, Wo
         out = torch.empty(B, self.out_channels, H, W, dtype=torch.float32, device=self._device)
         ops.gemm(h, w["conv_out"], out, conv=dict(B=B, Hi=H, Wi=W, Ho=H, Wo=W), rows_per_batch=H * W, epilogue=ops.EPI_NCHW_F32)
-        return out
+        return tap("conv_out", out)
 
     forward = __call__
 
@@ -105,10 +108,11 @@ class ImageProjModel_p(HipModel):
         if D != self.in_dim:
             raise ValueError(f"expected last dim {self.in_dim}, got {D}")
         M = B * L
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
         xb = ops.f32_to_bf16(x.to(self._device, torch.float32).contiguous().view(M, D), self._buf("x", (M, D)))
-        h = ops.gemm(xb, w["fc1"], self._buf("h", (M, self.hidden_dim)), act=ops.ACT_GELU)
-        n = ops.layernorm(h, w["ln"][0], w["ln"][1], 1e-5, self._buf("n", (M, self.hidden_dim)))
-        y = ops.gemm(n, w["fc2"], torch.empty(M, self.out_dim, dtype=BF16, device=self._device))
+        h = ops.gemm(tap("x", xb), w["fc1"], self._buf("h", (M, self.hidden_dim)), act=ops.ACT_GELU)
+        n = ops.layernorm(tap("h", h), w["ln"][0], w["ln"][1], 1e-5, self._buf("n", (M, self.hidden_dim)))
+        y = tap("y", ops.gemm(tap("n", n), w["fc2"], torch.empty(M, self.out_dim, dtype=BF16, device=self._device)))
         return y.view(B, L, self.out_dim).to(x.dtype if x.dtype.is_floating_point else torch.float32)
 
     forward = __call__
@@ -146,10 +150,12 @@ class ImageProjection(HipModel):
         if x.shape[1] != E:
             raise ValueError(f"expected last dim {E}, got {x.shape[1]}")
         M = x.shape[0]
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
         xb = ops.f32_to_bf16(x.to(self._device, torch.float32).contiguous(), self._buf("x", (M, E)))
-        h = ops.gemm(xb, w["fc1"], self._buf("h", (M, 2 * E)), act=ops.ACT_GELU)
-        y = ops.gemm(h, w["fc2"], self._buf("y", (M, D * T)))
-        n = ops.layernorm(y.view(M * T, D), w["ln"][0], w["ln"][1], 1e-5, torch.empty(M * T, D, dtype=BF16, device=self._device))
+        h = ops.gemm(tap("x", xb), w["fc1"], self._buf("h", (M, 2 * E)), act=ops.ACT_GELU)
+        y = ops.gemm(tap("h", h), w["fc2"], self._buf("y", (M, D * T)))
+        n = ops.layernorm(tap("y", y).view(M * T, D), w["ln"][0], w["ln"][1], 1e-5, torch.empty(M * T, D, dtype=BF16, device=self._device))
+        tap("n", n)
         return n.view(M, T, D).to(id_embeds.dtype if id_embeds.dtype.is_floating_point else torch.float32)
 
     forward = __call__

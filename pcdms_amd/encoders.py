@@ -198,23 +198,34 @@ class Dinov2Model(HipModel):
         for b in range(B):   # epilogue: + bias + position embedding row (m % (gh*gw)), written below the CLS row
             ops.gemm(colb[b], w["patch"], xv[b, 1:], residual=pos[1:], res_mod=gh * gw)
             xv[b, 0].copy_(pos[0])
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
+        tap("cols", colb), tap("pos", pos), tap("emb", x)
         H = c.num_attention_heads
         Tp = (T + 7) // 8 * 8
         Fp = w["layers"][0]["down"].K
-        for L in w["layers"]:
+        for i, L in enumerate(w["layers"]):
+            p = f"layer.{i}."
             n = ops.layernorm(x, L["n1"][0], L["n1"][1], c.layer_norm_eps, self._buf("ln", (M, D)))
+            tap(p + "ln1", n)
             qk = self._buf("qk", (M, 2 * D))
             vt = self._buf("vt", (B, D, Tp), zero=True)
             ops.gemm(n, L["qkv"], qk, rows_per_batch=T, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * D)
+            tap(p + "qk", qk), tap(p + "vt", vt)
             at = ops.flash_attn(qk[:, :D], qk[:, D:], vt, self._buf("at", (M, D)), B, H, T, T)
+            tap(p + "at", at)
             x1 = ops.gemm(at, L["o"], self._buf("tok_b", (M, D)), residual=x, res_mod=M)
+            tap(p + "x1", x1)
             n = ops.layernorm(x1, L["n2"][0], L["n2"][1], c.layer_norm_eps, self._buf("ln", (M, D)))
+            tap(p + "ln2", n)
             if "glu" in L:
                 f = ops.gemm(n, L["glu"], self._buf("ff", (M, Fp), zero=True), epilogue=ops.EPI_GEGLU, act=ops.ACT_SILU)
             else:
                 f = ops.gemm(n, L["fc1"], self._buf("ff", (M, Fp)), act=ops.ACT_GELU)
+            tap(p + "ff", f)
             x = ops.gemm(f, L["down"], self._buf("tok_a", (M, D)), residual=x1, res_mod=M)
+            tap(p + "x", x)
         out = ops.layernorm(x, w["norm"][0], w["norm"][1], c.layer_norm_eps, self._buf("out", (M, D)))
+        tap("out", out)
         hs = out.view(B, T, D).to(pixel_values.dtype if pixel_values.dtype.is_floating_point else torch.float32)
         res = BaseModelOutputWithPooling(hs, hs[:, 0])
         return res if return_dict else (res.last_hidden_state, res.pooler_output)
@@ -331,23 +342,26 @@ class CLIPVisionModelWithProjection(HipModel):
                                     o=lin(a + "out_proj"), fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
         self._w = w
 
-    def _attention(self, n, L, B, T):
-        """softmax(q k^T / sqrt(dh)) v for every (image, head); returns [B*T, D]."""
+    def _attention(self, n, L, B, T, p=""):
+        """softmax(q k^T / sqrt(dh)) v for every (image, head); returns [B*T, D].  ``p``: the layer's prefix for the test hook."""
         w, c, D = self._w, self.config, self.config.hidden_size
         H, dh, dhp = c.num_attention_heads, w["dh"], w["dhp"]
         M = B * T
         QW = H * dhp
         qk = self._buf("qk", (M + 64, 2 * QW), zero=True)[:M + 4]       # zero tail rows: read (never used) by the padded N-tiles
         at = self._buf("at", (M, D))
+        tap = self._tap
         if dh == 64:
             vt = self._buf("vt", (B, D, (T + 7) // 8 * 8), zero=True)
             ops.gemm(n, L["qkv"], qk[:M], rows_per_batch=T, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * QW)
+            tap(p + "qk", qk), tap(p + "vt", vt)
             return ops.flash_attn(qk[:M, :QW], qk[:M, QW:], vt, at, B, H, T, T)
         Tk = ops._round_up(T, 64)                 # key axis padded to the GEMM's K granularity (zero columns)
         Tq = ops._round_up(T, 4)                  # query axis padded to the GEMM's N granularity (rows >= T are never read back)
         flat = self._buf("vt", (B * D * Tk + 64 * Tk,), zero=True)      # tail: the last head's N-tile reads past its dh rows
         vt = flat[:B * D * Tk].view(B, D, Tk)
         ops.gemm(n, L["qkv"], qk[:M], rows_per_batch=T, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * QW)
+        tap(p + "qk", qk), tap(p + "vt", vt)
         S = self._buf("S", (B * H, Tq, T), torch.float32)
         P = self._buf("P", (B * H, Tq, Tk), zero=True)                  # columns >= T stay zero
         for b in range(B):
@@ -357,7 +371,9 @@ class CLIPVisionModelWithProjection(HipModel):
                 q = qk[b * T:b * T + Tq, h * dhp:(h + 1) * dhp]         # Tq - T rows of the next image / of the zero tail
                 wq = ops.PackedWeight(q, None, Tq, dhp, ops._round_up(Tq, 64), alg_nk=T * dh)
                 ops.gemm(k, wq, S[b * H + h], rows_per_batch=T, epilogue=ops.EPI_NCHW_F32, w_ld=2 * QW)
+        tap(p + "S", S)
         ops.softmax_rows(S.view(B * H * Tq, T), P.view(B * H * Tq, Tk), dh ** -0.5)
+        tap(p + "P", P)
         for b in range(B):
             for h in range(H):
                 wv = ops.PackedWeight(vt[b, h * dh:], None, dh, Tk, ops._round_up(dh, 64), alg_nk=dh * T)   # V_h^T [dh, Tk]
@@ -389,19 +405,32 @@ class CLIPVisionModelWithProjection(HipModel):
         for b in range(B):
             ops.gemm(colb[b], w["patch"], ev[b, 1:], residual=w["pos"][1:], res_mod=g * g)
             ev[b, 0].copy_(w["pos"][0])
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
+        tap("cols", colb), tap("pos", w["pos"]), tap("emb", e)
         x = ops.layernorm(e, w["pre"][0], w["pre"][1], c.layer_norm_eps, self._buf("tok_a", (M, D)))
-        for L in w["layers"]:
+        tap("pre", x)
+        for i, L in enumerate(w["layers"]):
+            p = f"layers.{i}."
             n = ops.layernorm(x, L["n1"][0], L["n1"][1], c.layer_norm_eps, self._buf("ln", (M, D)))
-            at = self._attention(n, L, B, T)
+            tap(p + "ln1", n)
+            at = self._attention(n, L, B, T, p)
+            tap(p + "at", at)
             x1 = ops.gemm(at, L["o"], self._buf("tok_b", (M, D)), residual=x, res_mod=M)
+            tap(p + "x1", x1)
             n = ops.layernorm(x1, L["n2"][0], L["n2"][1], c.layer_norm_eps, self._buf("ln", (M, D)))
+            tap(p + "ln2", n)
             f = ops.gemm(n, L["fc1"], self._buf("ff", (M, c.intermediate_size)), act=ops.ACT_GELU)
+            tap(p + "ff", f)
             x = ops.gemm(f, L["fc2"], self._buf("tok_a", (M, D)), residual=x1, res_mod=M)
+            tap(p + "x", x)
         cls_rows = self._buf("cls", (B, D))
         cls_rows.copy_(x.view(B, T, D)[:, 0])                                       # gather of the CLS rows (copy)
+        tap("cls", cls_rows)
         pooled = ops.layernorm(cls_rows, w["post"][0], w["post"][1], c.layer_norm_eps, self._buf("pooled", (B, D)))
+        tap("pooled", pooled)
         emb = torch.empty(B, c.projection_dim, dtype=torch.float32, device=self._device)
         ops.gemm(pooled, w["proj"], emb, rows_per_batch=1, epilogue=ops.EPI_NCHW_F32)   # fp32 [B, projection_dim]
+        tap("image_embeds", emb)
         od = pixel_values.dtype if pixel_values.dtype.is_floating_point else torch.float32
         out = CLIPVisionModelOutput(emb.to(od), x.view(B, T, D).to(od))
         return out if return_dict else (out.image_embeds, out.last_hidden_state)

@@ -177,14 +177,16 @@ class Stage1_PriorTransformer(HipModel):
         key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (proj_embedding, ehs, ehs1)) + (B,)
         if self._static is not None and self._static[0] == key:
             return
-        w, E = self._w, self.config.embedding_dim
+        w, E, tap = self._w, self.config.embedding_dim, self._tap
         for j, (x, pw, proj) in enumerate(((ehs, w["pose"], w["ehsp"]), (ehs1, w["pose1"], w["ehsp1"]))):
-            h = ops.gemm(self._in_bf16("pose_in", x, B, 64), pw["l0"], self._buf("pose_h", (B, _POSE_HIDDEN)), act=ops.ACT_GELU)
-            h = ops.layernorm(h, pw["n3"][0], pw["n3"][1], 1e-5, self._buf("pose_hn", (B, _POSE_HIDDEN)))
-            h = ops.gemm(h, pw["l4"], self._buf("pose_o", (B, _POSE_OUT)))
-            h = ops.layernorm(h, pw["n6"][0], pw["n6"][1], 1e-5, self._buf("pose_on", (B, _POSE_OUT)))
-            ops.gemm(h, proj, self._token(tokens, j), residual=w["pos"][j:j + 1], res_mod=1)
-        ops.gemm(self._in_bf16("emb_in", proj_embedding, B, E), w["emb"], self._token(tokens, 2), residual=w["pos"][2:3], res_mod=1)
+            xin = tap(f"pose{j}.in", self._in_bf16("pose_in", x, B, 64))
+            h = ops.gemm(xin, pw["l0"], self._buf("pose_h", (B, _POSE_HIDDEN)), act=ops.ACT_GELU)
+            h = ops.layernorm(tap(f"pose{j}.h", h), pw["n3"][0], pw["n3"][1], 1e-5, self._buf("pose_hn", (B, _POSE_HIDDEN)))
+            h = ops.gemm(tap(f"pose{j}.hn", h), pw["l4"], self._buf("pose_o", (B, _POSE_OUT)))
+            h = ops.layernorm(tap(f"pose{j}.o", h), pw["n6"][0], pw["n6"][1], 1e-5, self._buf("pose_on", (B, _POSE_OUT)))
+            ops.gemm(tap(f"pose{j}.on", h), proj, self._token(tokens, j), residual=w["pos"][j:j + 1], res_mod=1)
+        xin = tap("emb_in", self._in_bf16("emb_in", proj_embedding, B, E))
+        ops.gemm(xin, w["emb"], self._token(tokens, 2), residual=w["pos"][2:3], res_mod=1)
         self._token(tokens, self.num_tokens - 1).copy_(w["prd"])    # device-to-device copy of a load-time constant
         self._static = (key, proj_embedding, ehs, ehs1)             # (keeps the keyed tensors alive)
 
@@ -216,26 +218,34 @@ class Stage1_PriorTransformer(HipModel):
         tokens = self._buf("tokens", (M, D))
         self._static_tokens(tokens, proj_embedding, encoder_hidden_states, encoder_hidden_states1, B)
         # time token: sinusoid -> Linear+SiLU -> Linear (+ positional row 3)
+        tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
         sin = ops.timestep_embedding(t_dev, _step_dev, self._buf("sin", (B, D), torch.float32), flip=True, shift=0.0)
-        th = ops.gemm(ops.f32_to_bf16(sin, self._buf("sinb", (B, D))), w["t1"], self._buf("th", (B, D)), act=ops.ACT_SILU)
-        ops.gemm(th, w["t2"], self._token(tokens, 3), residual=w["pos"][3:4], res_mod=1)
+        sinb = ops.f32_to_bf16(tap("sin", sin), self._buf("sinb", (B, D)))
+        th = ops.gemm(tap("sinb", sinb), w["t1"], self._buf("th", (B, D)), act=ops.ACT_SILU)
+        ops.gemm(tap("th", th), w["t2"], self._token(tokens, 3), residual=w["pos"][3:4], res_mod=1)
         # x_t token
-        ops.gemm(self._in_bf16("x_in", hidden_states, B, E), w["proj_in"], self._token(tokens, 4), residual=w["pos"][4:5], res_mod=1)
-        x = tokens
+        xin = tap("x_in", self._in_bf16("x_in", hidden_states, B, E))
+        ops.gemm(xin, w["proj_in"], self._token(tokens, 4), residual=w["pos"][4:5], res_mod=1)
+        x = tap("tokens", tokens)
         H = c.num_attention_heads
         for i, blk in enumerate(w["blocks"]):
+            p = f"blocks.{i}."
             n = ops.layernorm(x, blk["n1"][0], blk["n1"][1], 1e-5, self._buf("ln", (M, D)))
+            tap(p + "ln1", n)
             qk = self._buf("qk", (M, 2 * D))
             vt = self._buf("vt", (B, D, 8), zero=True)
             ops.gemm(n, blk["qkv"], qk, rows_per_batch=T, epilogue=ops.EPI_SPLIT_VT, out2=vt, vt_col0=2 * D)
+            tap(p + "qk", qk), tap(p + "vt", vt)
             at = ops.flash_attn(qk[:, :D], qk[:, D:], vt, self._buf("at", (M, D)), B, H, T, T)
-            x1 = ops.gemm(at, blk["o"], self._buf("xa", (M, D)), residual=x, res_mod=M)
-            n = ops.layernorm(x1, blk["n3"][0], blk["n3"][1], 1e-5, self._buf("ln", (M, D)))
-            f = ops.gemm(n, blk["ff1"], self._buf("ff", (M, 4 * D)), act=ops.ACT_GELU)
-            x = ops.gemm(f, blk["ff2"], self._buf("xb", (M, D)), residual=x1, res_mod=M)
+            x1 = ops.gemm(tap(p + "at", at), blk["o"], self._buf("xa", (M, D)), residual=x, res_mod=M)
+            n = ops.layernorm(tap(p + "x1", x1), blk["n3"][0], blk["n3"][1], 1e-5, self._buf("ln", (M, D)))
+            f = ops.gemm(tap(p + "ln3", n), blk["ff1"], self._buf("ff", (M, 4 * D)), act=ops.ACT_GELU)
+            x = ops.gemm(tap(p + "ff", f), blk["ff2"], self._buf("xb", (M, D)), residual=x1, res_mod=M)
+            tap(p + "x", x)
         n = ops.layernorm(x, w["norm_out"][0], w["norm_out"][1], 1e-5, self._buf("ln", (M, D)))
         o = self._buf("out", (B, E, T), torch.float32)
-        ops.gemm(n, w["out"], o, rows_per_batch=T, epilogue=ops.EPI_NCHW_F32)     # fp32 [B, E, T]
+        ops.gemm(tap("norm_out", n), w["out"], o, rows_per_batch=T, epilogue=ops.EPI_NCHW_F32)     # fp32 [B, E, T]
+        tap("out", o)
         pred = o[:, :, T - 1].contiguous()                                          # hidden_states[:, -1] (:291)
         return PriorTransformerOutput(pred) if return_dict else (pred,)
 

@@ -837,7 +837,8 @@ def _seen(pl: Plan, sd, raw):
     best: Dict[str, float] = {}
     for name, key, st, kw in _fault_list(pl, sd):
         bad = st.run(kw["sd"], T, torch.float64, ident, fault=kw.get("fault"), sub=kw.get("sub"))
-        ratio = rel(T[st.name], bad) / max(unit[st.name], 1e-300)
+        # (a fault that changes the stage's shape is seen by ``compare``'s shape assertion)
+        ratio = rel(T[st.name], bad) / max(unit[st.name], 1e-300) if bad.shape == T[st.name].shape else math.inf
         fid = name.split("@")[0] if key is not None else name   # a parameter fault is seen if ANY stage that reads the tensor sees it
         best[fid] = max(best.get(fid, 0.0), ratio)
     return best
@@ -891,9 +892,12 @@ if __name__ == "__main__":   # refresh profiles/schedule_conformance_values.json
         cases.update(json.loads(VALUES_OUT.read_text()))
     uf = VALUES_OUT.parent / "schedule_conformance_unseen_faults.json"
     faults = json.loads(uf.read_text()) if uf.exists() else dict(faults=old.get("faults", 0), unseen=old.get("unseen_faults", {}))
+    uc = VALUES_OUT.parent / "cond_stack_unseen_faults.json"   # (tests/test_cond_stack_conformance.py)
+    cs = json.loads(uc.read_text()) if uc.exists() else dict(faults=old.get("cond_stack_faults", 0), unseen=old.get("cond_stack_unseen_faults", {}))
     dst.write_text(json.dumps(dict(
         note="per stage: e_ref = rel-L2 of the bf16-boundary yardstick from fp64, device = rel-L2 of the product from fp64 (teacher forcing), "
              "ratio = device in units of the stage's bound / 2 (<= 2 passes); emu/ = lane emulator, gpu/ = MI355X.  unseen_faults: the faults of "
-             "test_faults_are_seen that move their stage by less than 4 x e_ref (value = the multiple reached)  (tests/test_schedule_conformance.py)",
-        faults=faults["faults"], unseen_faults=faults["unseen"], cases=cases), indent=0, sort_keys=True) + "\n")
+             "test_faults_are_seen that move their stage by less than 4 x e_ref (value = the multiple reached); cond_stack_*: the same for tests/test_cond_stack_conformance.py  (tests/test_schedule_conformance.py)",
+        faults=faults["faults"], unseen_faults=faults["unseen"], cond_stack_faults=cs["faults"], cond_stack_unseen_faults=cs["unseen"],
+        cases=cases), indent=0, sort_keys=True) + "\n")
     print(dst, len(cases), "cases;", len(faults["unseen"]), "of", faults["faults"], "faults unseen")
