@@ -557,6 +557,109 @@ int pcdm_pose_draw(const float* keypoints, const float* scores, int M, int P, in
                    void* ws, int64_t ws_bytes, pcdm_stream_t s);
 int pcdm_resize_linear_u8(const void* src, int M, int Hs, int Ws, void* dst, int Hd, int Wd, pcdm_stream_t s);
 
+/* ---- The whole-body pose estimator: image + person boxes -> 133 keypoints and scores per box (what Wholebody.__call__ gets from its second
+ * network, the top-down DWPose-l of mmpose: CSPNeXt-l backbone, RTMCC head, SimCC decoding).  The person detector (YOLOX-l) is NOT here: boxes come
+ * from the caller.  mmpose and mmdet are not dependencies; the network is restated from its published definition below, and parity with mmpose on
+ * the published checkpoint is NOT pinned by a test that runs by default (tests/test_dwpose.py holds a dormant pin) -- the same standing as LPIPS, FID
+ * and the OpenCV rules.  Everything is fp32; activations are NHWC with channels padded to multiples of 4 (padding channels exactly 0).  The schedule
+ * is one C call, pcdm_dwpose_forward, or the same launches driven from the host (pcdms_amd/pose.py: DWPoseEstimator); these are its kernels.  No atomics, no allocation, no host synchronisation, fixed
+ * summation orders: reruns are bit-identical and a crop's result does not depend on its place in the batch.  Arguments outside the stated ranges
+ * return -1 and write nothing.
+ *
+ * Box -> crop (GetBBoxCenterScale, TopdownAffine without UDP), fp32, every operation its own: c = ((x1 + x2) 0.5, (y1 + y2) 0.5),
+ *   (w, h) = (x2 - x1, y2 - y1) 1.25; ar = Win / Hin: if w > h ar then h = w / ar else w = h ar.  The warp is one scale s = Win / w about the centre
+ *   (no rotation; mmpose derives it from the widths), destination centre (0.5 Win, 0.5 Hin).
+ * pcdm_pose_crop: images uint8 [N, H, W, 3] (RGB), boxes fp32 [R, 4] = (x1, y1, x2, y2) in DEVICE memory, image_index int32 [R] on the device (NULL:
+ *   image 0; an index outside [0, N) gives a black crop) -> out fp32 NHWC [R or 2 R, Hin, Win, 4].  Sampling is this library's statement of OpenCV's
+ *   8-bit warpAffine(INTER_LINEAR, BORDER_CONSTANT 0): in double, inv = w / Win, bx = cx - 0.5 Win inv, by = cy - 0.5 Hin inv (the inverse map
+ *   xs = (xd - 0.5 Win) / s + cx split into its two terms); X = (rint(bx 1024) + 16 + rint(inv xd 1024)) >> 5, Y likewise from by and yd (rint: half
+ *   to even, saturated to int32, NaN the lower bound; 64-bit sums): a 1/32 sub-pixel grid, sx = X >> 5, fx = X & 31.  The four weights of the
+ *   32 x 32 table at scale 2^15 are exact products, (32 - fx)(32 - fy) 32, fx (32 - fy) 32, (32 - fx) fy 32, fx fy 32 (sum 2^15; the table is not
+ *   stored); pixels outside the image are 0; value = (sum + 2^14) >> 15 per channel.  Then (value - mean_c) / std_c in fp32 with mean (123.675,
+ *   116.28, 103.53), std (58.395, 57.12, 57.375); channel 3 = 0.  flip: crops R .. 2 R - 1 are crops 0 .. R - 1 mirrored in x (destination column
+ *   Win - 1 - x of the SAME crop, not a warp of the mirrored image).  One launch.  Hin, Win <= 4096.
+ * pcdm_conv2d_f32_act: pcdm_conv2d_f32_ex (same packed weights, same k order) plus: the input is the channel slice [in_offset, in_offset + Cin) of
+ *   an NHWC tensor with in_pitch channels per pixel (both multiples of 4); act 0 none, 1 ReLU, 2 SiLU = v / (1 + exp(-v)); residual (or NULL): the
+ *   slice [res_offset, res_offset + Cout) of an NHWC tensor [B, Ho, Wo, res_pitch], added AFTER the activation (it may be the output slice itself);
+ *   a_scale (or NULL): fp32 [B, Cin], 16-byte aligned: the A operand of image b, channel c is x a_scale[b, c] (one fp32 product) -- the channel
+ *   attention folded into the convolution that consumes it.  The output slice must not overlap the INPUT slice (-1 when both are slices of one
+ *   tensor of one pitch; other aliasing is the caller's to avoid); this holds for pcdm_dwconv5_silu_f32 and pcdm_maxpool5_f32 too.  With in_pitch = Cin, in_offset = 0, act <= 1, no residual and no a_scale the result
+ *   is bit for bit pcdm_conv2d_f32_ex's.  A linear layer is the 1 x 1 case with B = 1, Hi = 1, Wi = rows.
+ * pcdm_dwconv5_silu_f32: depthwise 5 x 5, pad 2, stride 1, + bias, SiLU on the slice [in_offset, +C) of [B, H, W, in_pitch] into the slice
+ *   [out_offset, +C) of [B, H, W, out_pitch]; w fp32 [25, C] (tap ky 5 + kx, then channel), bias [C]; C, pitches, offsets multiples of 4.  One
+ *   fmaf chain per output over the taps in (ky, kx) order, taps outside the image skipped.
+ * pcdm_maxpool5_f32: MaxPool2d(5, stride 1, pad 2) between channel slices as above (the two may be disjoint slices of one tensor): the padding never
+ *   wins, a NaN does.  SPP's 5 / 9 / 13 pools are this one cascaded, which is exact for a maximum.
+ * pcdm_fc_hsigmoid_f32: out[b, n] = clamp(sum_c w[n, c] x[b, c] + bias[n] + 3, 0, 6) / 6 for x fp32 [B, C], w [C, C]: ChannelAttention's vector
+ *   from pcdm_global_avgpool_f32's means.
+ * pcdm_scalenorm_f32: out[b rows + k, i] = x / max(|x|_2 dim^-0.5, eps) g[0] over i < dim, element i of row (b, k) at x[b batch_stride + k row_stride
+ *   + i elem_stride]; columns dim .. out_pitch - 1 are written 0.  side_out (with side_scale fp32 [dim], or both NULL): side_out[row, i] =
+ *   x side_scale[i].  g in device memory.
+ * pcdm_gau_core_f32: uv fp32 [B T, 2 e + 128] = (u | v | base) per token, gamma / beta fp32 [2, 128]: q = base gamma[0] + beta[0], k = base gamma[1] +
+ *   beta[1], A = relu(q k^T / sqrt(128))^2 over the T tokens of a crop, out fp32 [B T, e] = u (A v).  T <= 256, e a multiple of 4.
+ * pcdm_simcc_decode: simcc_x fp32 [R2 K, x_pitch] (x_bins logits), simcc_y [R2 K, y_pitch] (y_bins), R2 = 2 R with flip: crop R + r is crop r
+ *   mirrored, its output for keypoint k is row flip_idx[k] (int32 [K] on the device) with the x bins reversed; merged = 0.5 (plain + flipped).  Per
+ *   axis loc = argmax (np.argmax: the first maximum, a NaN ranks highest); score = max_x > max_y ? max_y : max_x (raw logits); both loc = -1 where
+ *   score <= 0; keypoints [R, K, 2] = (loc / 2) / (Win, Hin) (w, h) + c - 0.5 (w, h) in fp32, each operation its own; scores [R, K].
+ *
+ * The network (Conv = convolution without bias + BatchNorm(eps 1e-5: the config's bare SyncBN) + SiLU, the BatchNorm folded on the host in fp64):
+ *   stem: Conv 3x3 s2 3 -> 32, Conv 3x3 32 -> 32, Conv 3x3 32 -> 64.  Four stages (in, out, blocks, identity, spp) = (64, 128, 3, yes, no),
+ *   (128, 256, 6, yes, no), (256, 512, 6, yes, no), (512, 1024, 3, no, yes): Conv 3x3 s2 in -> out; with spp: Conv 1x1 out -> out/2, max-pools 5 / 9
+ *   / 13 (stride 1, same size), cat [x, p5, p9, p13], Conv 1x1 2 out -> out; then the CSP layer, mid = out / 2: main = Conv 1x1 -> mid, short = Conv
+ *   1x1 -> mid, the blocks on main (Conv 3x3 mid -> mid; depthwise 5x5 + BN + SiLU; Conv 1x1 mid -> mid; + input when identity), cat (main, short),
+ *   x hardsigmoid(fc(global mean(x))) with fc a 1x1 convolution with bias, Conv 1x1 -> out.  Head on the stride-32 map [h, w] of 1024 channels:
+ *   Conv2d 7x7 pad 3 with bias -> K maps, flattened to [K, h w]; ScaleNorm(h w); Linear(h w -> 256); GAU: hn = ScaleNorm(256)(x), (u, v, base) =
+ *   split(SiLU(Linear(256 -> 1152)(hn)), 512, 512, 128), the core above, x res_scale + Linear(512 -> 256)(core); Linear(256 -> 2 Win) and
+ *   Linear(256 -> 2 Hin) give the SimCC logits.  No linear has a bias. */
+/* pcdm_dwpose_forward: the whole estimator as ONE C call (as pcdm_inception_features): crop, backbone, head and decode, 60-odd launches on the
+ *   caller's stream, on one caller-owned workspace of pcdm_dwpose_ws_bytes(cfg, R, flip) bytes (16-byte aligned), keypoints fp32 [R, K, 2] and scores
+ *   fp32 [R, K] out.  Bit for bit the per-kernel calls above in the same order (pcdms_amd/pose.py runs either).  cfg: the crop size, K <= 256, the
+ *   stem's and the four stages' output channels (multiples of 8), blocks per stage, identity / spp flags.  wts: HOST arrays of DEVICE pointers --
+ *   conv_w / conv_b [n_conv]: the packed convolutions (pcdm_pack_lpips_conv, BatchNorm folded) in schedule order: stem 0, 1, 2; per stage: the
+ *   strided convolution, (spp: conv1, conv2,) main_conv, short_conv, per block conv1 and pointwise_conv, final_conv; then final_layer, mlp.1,
+ *   gau.uv, gau.o, and cls_x and cls_y as ONE linear (x rows first); dw_w / dw_b [n_dw]: the depthwise layers in block order ([25, C] and [C]);
+ *   fc_w / fc_b: the four attention layers; mlp_g, ln_g ([1]), gamma, beta ([2, 128]), res_scale ([256]); flip_idx (int32 [K]; may be NULL
+ *   without flip).  -1 and nothing written for a NULL pointer, counts that do not match cfg, or sizes outside the ranges above. */
+typedef struct pcdm_dwpose_config {
+    int32_t Hin, Win, K;
+    int32_t stem;
+    int32_t n_stages;               /* 4 */
+    int32_t out[4], blocks[4], identity[4], spp[4];
+} pcdm_dwpose_config;
+typedef struct pcdm_dwpose_weights {
+    const float* const* conv_w;
+    const float* const* conv_b;
+    const float* const* dw_w;
+    const float* const* dw_b;
+    int32_t n_conv, n_dw;
+    const float* fc_w[4];
+    const float* fc_b[4];
+    const float* mlp_g;
+    const float* ln_g;
+    const float* gamma;
+    const float* beta;
+    const float* res_scale;
+    const int32_t* flip_idx;
+} pcdm_dwpose_weights;
+int64_t pcdm_dwpose_ws_bytes(const pcdm_dwpose_config* cfg, int R, int flip);
+int pcdm_dwpose_forward(const void* images, int N, int H, int W, const float* boxes, const int32_t* image_index, int R, int flip,
+                        const pcdm_dwpose_config* cfg, const pcdm_dwpose_weights* wts, float* keypoints, float* scores, void* ws, int64_t ws_bytes,
+                        pcdm_stream_t s);
+int pcdm_pose_crop(const void* images, int N, int H, int W, const float* boxes, const int32_t* image_index, int R, int flip, int Hin, int Win, float* out,
+                   pcdm_stream_t s);
+int pcdm_conv2d_f32_act(const float* x, int B, int Hi, int Wi, int Cin, int in_pitch, int in_offset, const float* w_packed, const float* bias, int Cout,
+                        int kh, int kw, int stride, int pad_h, int pad_w, int act, const float* residual, int res_pitch, int res_offset,
+                        const float* a_scale, float* out, int out_pitch, int out_offset, pcdm_stream_t s);
+int pcdm_dwconv5_silu_f32(const float* x, int B, int H, int W, int C, int in_pitch, int in_offset, const float* w, const float* bias, float* out,
+                          int out_pitch, int out_offset, pcdm_stream_t s);
+int pcdm_maxpool5_f32(const float* x, int B, int H, int W, int C, int in_pitch, int in_offset, float* out, int out_pitch, int out_offset, pcdm_stream_t s);
+int pcdm_fc_hsigmoid_f32(const float* x, int B, int C, const float* w, const float* bias, float* out, pcdm_stream_t s);
+int pcdm_scalenorm_f32(const float* x, int B, int rows, int dim, int64_t batch_stride, int64_t row_stride, int64_t elem_stride, float eps, const float* g,
+                       float* out, int out_pitch, const float* side_scale, float* side_out, int side_pitch, pcdm_stream_t s);
+int pcdm_gau_core_f32(const float* uv, int B, int T, int e, const float* gamma, const float* beta, float* out, pcdm_stream_t s);
+int pcdm_simcc_decode(const float* simcc_x, int x_pitch, int x_bins, const float* simcc_y, int y_pitch, int y_bins, int R, int K, int flip,
+                      const int32_t* flip_idx, const float* boxes, int Hin, int Win, float* keypoints, float* scores, pcdm_stream_t s);
+
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host
  * that is not Python: pcdm_unet_create from the topology, pcdm_unet_set_weight / _set_vector with the packed tensors under their

@@ -82,6 +82,21 @@ class InceptionWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 94), ("bias", C.c_void_p * 94)]
 
 
+class DWPoseConfig(C.Structure):
+    """Mirror of ``pcdm_dwpose_config`` (include/pcdm.h)."""
+
+    _fields_ = [("Hin", C.c_int32), ("Win", C.c_int32), ("K", C.c_int32), ("stem", C.c_int32), ("n_stages", C.c_int32), ("out", C.c_int32 * 4),
+                ("blocks", C.c_int32 * 4), ("identity", C.c_int32 * 4), ("spp", C.c_int32 * 4)]
+
+
+class DWPoseWeights(C.Structure):
+    """Mirror of ``pcdm_dwpose_weights`` (include/pcdm.h)."""
+
+    _fields_ = [("conv_w", C.POINTER(C.c_void_p)), ("conv_b", C.POINTER(C.c_void_p)), ("dw_w", C.POINTER(C.c_void_p)), ("dw_b", C.POINTER(C.c_void_p)),
+                ("n_conv", C.c_int32), ("n_dw", C.c_int32), ("fc_w", C.c_void_p * 4), ("fc_b", C.c_void_p * 4), ("mlp_g", C.c_void_p),
+                ("ln_g", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("res_scale", C.c_void_p), ("flip_idx", C.c_void_p)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
 _SIGS = {
@@ -147,6 +162,16 @@ _SIGS = {
     "pcdm_pose_ws_bytes": ([_I, _I], _L),
     "pcdm_pose_draw": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_resize_linear_u8": ([_P, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_pose_crop": ([_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_conv2d_f32_act": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P], C.c_int),
+    "pcdm_dwconv5_silu_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P], C.c_int),
+    "pcdm_maxpool5_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_fc_hsigmoid_f32": ([_P, _I, _I, _P, _P, _P, _P], C.c_int),
+    "pcdm_scalenorm_f32": ([_P, _I, _I, _I, _L, _L, _L, _F, _P, _P, _I, _P, _P, _I, _P], C.c_int),
+    "pcdm_gau_core_f32": ([_P, _I, _I, _I, _P, _P, _P, _P], C.c_int),
+    "pcdm_simcc_decode": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P], C.c_int),
+    "pcdm_dwpose_ws_bytes": ([C.POINTER(DWPoseConfig), _I, _I], _L),
+    "pcdm_dwpose_forward": ([_P, _I, _I, _I, _P, _P, _I, _I, C.POINTER(DWPoseConfig), C.POINTER(DWPoseWeights), _P, _P, _P, _L, _P], C.c_int),
     "pcdm_unet_create":([C.POINTER(UNetConfig)], _P),
     "pcdm_unet_destroy": ([_P], None),
     "pcdm_unet_last_error": ([_P], C.c_char_p),

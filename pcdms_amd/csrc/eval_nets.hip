@@ -49,6 +49,13 @@ struct ConvF32 {
     const float* bias;     // [Npad]
     float* out;            // channel 0 of the output slice: pixel m, channel n at out[m * ldo + n] (ldo = Cout: a tight NHWC [B, Ho, Wo, Cout])
     int Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, Kpad, M, relu, ldo;
+    // pcdm_conv2d_f32_act only (the EXT instance of the kernel): x = channel 0 of the input slice of an NHWC tensor with ldi channels per pixel;
+    // relu = the activation selector (0 none, 1 ReLU, 2 SiLU); res (or NULL): pixel m, channel n at res[m * ldr + n], added after the activation;
+    // ascale (or NULL): fp32 [B, Cin], the A operand of image b, input channel c is x * ascale[b * Cin + c]
+    int ldi;
+    const float* res;
+    int ldr;
+    const float* ascale;
 };
 
 // One wave = a 32 x 64 output tile (2 x 4 accumulators of 16 x 16: eight independent MFMA chains), four waves along M per workgroup, operands
@@ -57,6 +64,9 @@ struct ConvF32 {
 // not a clamped read -- and of its four weight columns, then runs four MFMA steps per accumulator (mfma_f32_16x16x4_quad).
 // The tap (ky, kx, c) of a lane advances by 16 channels per step without a division.  M and N tails: rows >= M load zeros and are not stored,
 // 16-column sub-tiles beyond Npad and the second row block of a tile that ends in the first are skipped (wave-uniform).
+// EXT = false: pcdm_conv2d_f32 / _ex exactly as they were (a tight input, bias + optional ReLU).  EXT = true: the extras of pcdm_conv2d_f32_act; the
+// k order, the fragments and the accumulation are the same, so with every extra off the two instances give the same bits.
+template <bool EXT>
 __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
     const int m0 = (blockIdx.x * 4 + wave) * 32, n0 = blockIdx.y * 64;
@@ -64,8 +74,10 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
     const int nsub = imin(4, (p.Npad - n0) / 16);
     const bool two = m0 + 16 < p.M;
     const float* xb[2];
+    const float* sc[2];
     int iy0[2], ix0[2];
     bool valid[2];
+    const int ldi = EXT ? p.ldi : p.Cin;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int m = m0 + 16 * t + r;
@@ -75,7 +87,8 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
         const int oy = q / p.Wo, ox = q - oy * p.Wo;
         iy0[t] = oy * p.stride - p.pad_h;
         ix0[t] = ox * p.stride - p.pad_w;
-        xb[t] = p.x + (int64_t)b * p.Hi * p.Wi * p.Cin;
+        xb[t] = p.x + (int64_t)b * p.Hi * p.Wi * ldi;
+        sc[t] = EXT && p.ascale ? p.ascale + (int64_t)b * p.Cin : nullptr;
     }
     f32x4 acc[2][4];
 #pragma unroll
@@ -94,7 +107,8 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
         for (int t = 0; t < 2; ++t) {
             const int iy = iy0[t] + ky, ix = ix0[t] + kx;
             const bool ok = valid[t] && ky < p.kh && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            a[t] = ok ? *(const f32x4*)(xb[t] + ((int64_t)iy * p.Wi + ix) * p.Cin + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+            a[t] = ok ? *(const f32x4*)(xb[t] + ((int64_t)iy * p.Wi + ix) * ldi + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (EXT && ok && sc[t]) a[t] = a[t] * *(const f32x4*)(sc[t] + c);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) b[j] = j < nsub ? *(const f32x4*)(wp + j * 64) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -123,7 +137,9 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32 p) {
                 const int m = m0 + 16 * t + 4 * g + e;
                 if (m >= p.M) continue;
                 float v = acc[t][j][e] + bv;
-                if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
+                if (EXT ? p.relu == 1 : p.relu != 0) v = v > 0.f ? v : (v != v ? v : 0.f);
+                if (EXT && p.relu == 2) v = v / (1.0f + expf(-v));
+                if (EXT && p.res) v += p.res[(int64_t)m * p.ldr + n];
                 p.out[(int64_t)m * p.ldo + n] = v;
             }
     }
@@ -259,8 +275,33 @@ inline int conv_f32_launch(const float* x, int B, int Hi, int Wi, int Cin, const
     const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
     const int Npad = (Cout + 15) / 16 * 16;
     if (M * ldo >= (int64_t)1 << 31 || (int64_t)B * Hi * Wi * Cin >= (int64_t)1 << 31 || K >= 1 << 24 || (Npad + 63) / 64 > 65535) return -1;
-    ConvF32 p{x, w, bias, out + off, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, (int)((K + 15) / 16 * 16), (int)M, relu, ldo};
-    PCDM_LAUNCH(conv_f32_kernel, dim3((unsigned)((M + 127) / 128), (Npad + 63) / 64), dim3(256), 0, s, p);
+    ConvF32 p{x, w, bias, out + off, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, (int)((K + 15) / 16 * 16), (int)M, relu, ldo,
+              Cin, nullptr, 0, nullptr};
+    PCDM_LAUNCH(conv_f32_kernel<false>, dim3((unsigned)((M + 127) / 128), (Npad + 63) / 64), dim3(256), 0, s, p);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+// pcdm_conv2d_f32_act: conv_f32_launch plus an input channel slice [in_off, in_off + Cin) of a tensor with ldi channels per pixel, the activation
+// selector, the residual slice [res_off, res_off + Cout) of a tensor with ldr channels per pixel and the A scale
+inline int conv_f32_act_launch(const float* x, int B, int Hi, int Wi, int Cin, int ldi, int in_off, const float* w, const float* bias, int Cout, int kh,
+                               int kw, int stride, int pad_h, int pad_w, int act, const float* res, int ldr, int res_off, const float* ascale,
+                               float* out, int ldo, int off, hipStream_t s) {
+    if (!x || !w || !bias || !out || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 4 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_h < 0 ||
+        pad_w < 0 || off < 0 || ldo < Cout || off > ldo - Cout || act < 0 || act > 2)
+        return -1;
+    if (in_off < 0 || in_off % 4 || ldi % 4 || ldi < Cin || in_off > ldi - Cin) return -1;
+    if (res && (res_off < 0 || ldr < Cout || res_off > ldr - Cout)) return -1;
+    if (x == out && ldi == ldo && in_off < off + Cout && off < in_off + Cin) return -1;   // the output slice overlaps the input slice of the same tensor
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)ascale) & 15) return -1;
+    if (Hi + 2 * (int64_t)pad_h < kh || Wi + 2 * (int64_t)pad_w < kw || pad_h >= 1 << 20 || pad_w >= 1 << 20) return -1;
+    const int Ho = (Hi + 2 * pad_h - kh) / stride + 1, Wo = (Wi + 2 * pad_w - kw) / stride + 1;
+    const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
+    const int Npad = (Cout + 15) / 16 * 16;
+    if (M * ldo >= (int64_t)1 << 31 || (int64_t)B * Hi * Wi * ldi >= (int64_t)1 << 31 || K >= 1 << 24 || (Npad + 63) / 64 > 65535) return -1;
+    if (res && M * ldr >= (int64_t)1 << 31) return -1;
+    ConvF32 p{x + in_off, w, bias, out + off, Hi, Wi, Cin, Ho, Wo, Cout, Npad, kh, kw, stride, pad_h, pad_w, (int)((K + 15) / 16 * 16), (int)M, act, ldo,
+              ldi, res ? res + res_off : nullptr, ldr, ascale};
+    PCDM_LAUNCH(conv_f32_kernel<true>, dim3((unsigned)((M + 127) / 128), (Npad + 63) / 64), dim3(256), 0, s, p);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -311,6 +352,13 @@ extern "C" int pcdm_maxpool3s2_f32(const float* x, int B, int Hi, int Wi, int C,
 extern "C" int pcdm_conv2d_f32_ex(const float* x, int B, int Hi, int Wi, int Cin, const float* w_packed, const float* bias, int Cout, int kh, int kw,
                                   int stride, int pad_h, int pad_w, int relu, float* out, int out_pitch, int out_offset, pcdm_stream_t s) {
     return conv_f32_launch(x, B, Hi, Wi, Cin, w_packed, bias, Cout, kh, kw, stride, pad_h, pad_w, relu, out, out_pitch, out_offset, (hipStream_t)s);
+}
+
+extern "C" int pcdm_conv2d_f32_act(const float* x, int B, int Hi, int Wi, int Cin, int in_pitch, int in_offset, const float* w_packed, const float* bias,
+                                   int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int act, const float* residual, int res_pitch,
+                                   int res_offset, const float* a_scale, float* out, int out_pitch, int out_offset, pcdm_stream_t s) {
+    return conv_f32_act_launch(x, B, Hi, Wi, Cin, in_pitch, in_offset, w_packed, bias, Cout, kh, kw, stride, pad_h, pad_w, act, residual, res_pitch,
+                               res_offset, a_scale, out, out_pitch, out_offset, (hipStream_t)s);
 }
 
 extern "C" int pcdm_maxpool3s2_f32_ex(const float* x, int B, int Hi, int Wi, int C, float* out, int out_pitch, int out_offset, pcdm_stream_t s) {

@@ -1113,7 +1113,8 @@ def global_avgpool_f32(x: torch.Tensor) -> torch.Tensor:
     _c(x, torch.float32)
     B, H, W, Cn = (int(v) for v in x.shape)
     out = torch.empty((B, Cn), dtype=torch.float32, device=x.device)
-    _chk(_lib.lib().pcdm_global_avgpool_f32(_ptr(x), B, H * W, Cn, _ptr(out), _stream(x)), "pcdm_global_avgpool_f32")
+    call = lambda: _lib.lib().pcdm_global_avgpool_f32(_ptr(x), B, H * W, Cn, _ptr(out), _stream(x))  # noqa: E731
+    _chk(_launch(x, call, "global_avgpool", float(x.numel()), (B, H, W, Cn)), "pcdm_global_avgpool_f32")
     return out
 
 
@@ -1259,3 +1260,175 @@ def resize_linear_u8(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
                                                     _stream(src))
     _chk(_launch(src, call, "resize_linear_u8", float(dst.numel()), tuple(src.shape[1:3]) + tuple(dst.shape[1:3])), "pcdm_resize_linear_u8")
     return dst
+
+
+# ------------------------------------------------------------------------------------ pose estimator (pcdms_amd/pose.py: DWPoseEstimator is the public surface)
+CONV_ACT_NONE, CONV_ACT_RELU, CONV_ACT_SILU = 0, 1, 2
+
+
+def pose_crop(images: torch.Tensor, boxes: torch.Tensor, image_index: Optional[torch.Tensor], size: Sequence[int], *, flip: bool) -> torch.Tensor:
+    """images uint8 [N, H, W, 3], boxes fp32 [R, 4] (x1, y1, x2, y2), image_index int32 [R] or None (image 0) -> the normalised crops fp32 NHWC
+    [R or 2 R, Hin, Win, 4], ``size`` = (Hin, Win); with ``flip`` the second half is the first mirrored in x (include/pcdm.h: pcdm_pose_crop)."""
+    _c(images, torch.uint8); _c(boxes, torch.float32)
+    assert images.dim() == 4 and images.shape[3] == 3 and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.device == images.device, \
+        (images.shape, boxes.shape)
+    N, H, W = (int(v) for v in images.shape[:3])
+    R, Hin, Win = int(boxes.shape[0]), int(size[0]), int(size[1])
+    if image_index is not None:
+        _c(image_index, torch.int32)
+        assert tuple(image_index.shape) == (R,) and image_index.device == images.device
+    out = torch.empty((R * (2 if flip else 1), Hin, Win, 4), dtype=torch.float32, device=images.device)
+    call = lambda: _lib.lib().pcdm_pose_crop(_ptr(images), N, H, W, _ptr(boxes), _ptr(image_index), R, int(bool(flip)), Hin, Win, _ptr(out),  # noqa: E731
+                                             _stream(images))
+    _chk(_launch(images, call, "pose_crop", float(out.numel()), (N, H, W, R, Hin, Win)), "pcdm_pose_crop")
+    return out
+
+
+def conv2d_f32_act(x: torch.Tensor, pw: dict, *, stride: int = 1, pad: Sequence[int] = (0, 0), act: int = CONV_ACT_NONE, in_offset: int = 0,
+                   residual: Optional[torch.Tensor] = None, res_offset: int = 0, a_scale: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, offset: int = 0) -> torch.Tensor:
+    """``conv2d_f32_ex`` reading the channels ``[in_offset, in_offset + pw["cin"])`` of ``x`` NHWC fp32 [B, Hi, Wi, pitch], with an activation
+    selector (``CONV_ACT_*``), an optional ``residual`` NHWC [B, Ho, Wo, pitch] whose channels ``[res_offset, res_offset + Cout)`` are added after the
+    activation, and an optional ``a_scale`` fp32 [B, Cin] multiplied into the input per image and channel (include/pcdm.h: pcdm_conv2d_f32_act)."""
+    _c(x, torch.float32)
+    B, Hi, Wi, ldi = (int(v) for v in x.shape)
+    Cin, Cout = pw["cin"], pw["cout"]
+    ph, pwd = int(pad[0]), int(pad[1])
+    Ho, Wo = (Hi + 2 * ph - pw["kh"]) // stride + 1, (Wi + 2 * pwd - pw["kw"]) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"a {pw['kh']} x {pw['kw']} kernel does not fit a {Hi} x {Wi} image padded by {(ph, pwd)}")
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    _c(out, torch.float32)
+    if out.dim() != 4 or tuple(out.shape[:3]) != (B, Ho, Wo) or out.device != x.device:
+        raise ValueError(f"out {tuple(out.shape)} on {out.device}: expected [{B}, {Ho}, {Wo}, pitch] on {x.device}")
+    ldr = 0
+    if residual is not None:
+        _c(residual, torch.float32)
+        if residual.dim() != 4 or tuple(residual.shape[:3]) != (B, Ho, Wo) or residual.device != x.device:
+            raise ValueError(f"residual {tuple(residual.shape)}: expected [{B}, {Ho}, {Wo}, pitch] on {x.device}")
+        ldr = int(residual.shape[3])
+    if a_scale is not None:
+        _c(a_scale, torch.float32)
+        if tuple(a_scale.shape) != (B, Cin) or a_scale.device != x.device:
+            raise ValueError(f"a_scale {tuple(a_scale.shape)}: expected [{B}, {Cin}] on {x.device}")
+    call = lambda: _lib.lib().pcdm_conv2d_f32_act(_ptr(x), B, Hi, Wi, Cin, ldi, int(in_offset), _ptr(pw["w"]), _ptr(pw["bias"]), Cout, pw["kh"],  # noqa: E731
+                                                  pw["kw"], int(stride), ph, pwd, int(act), _ptr(residual), ldr, int(res_offset), _ptr(a_scale),
+                                                  _ptr(out), int(out.shape[3]), int(offset), _stream(x))
+    work = 2.0 * B * Ho * Wo * Cout * pw["kh"] * pw["kw"] * Cin
+    _chk(_launch(x, call, "conv2d_f32_act", work, (B, Hi, Wi, Cin, Cout, pw["kh"], pw["kw"], stride)), "pcdm_conv2d_f32_act")
+    return out
+
+
+def dwconv5_silu_f32(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, *, in_offset: int = 0, offset: int = 0) -> torch.Tensor:
+    """Depthwise 5 x 5 (pad 2) + bias + SiLU of the channels ``[in_offset, in_offset + C)`` of ``x`` NHWC fp32 into the channels ``[offset, offset + C)``
+    of ``out``; ``w`` fp32 [25, C], ``bias`` [C] (include/pcdm.h: pcdm_dwconv5_silu_f32)."""
+    _c(x, torch.float32); _c(w, torch.float32); _c(bias, torch.float32); _c(out, torch.float32)
+    B, H, W, ldi = (int(v) for v in x.shape)
+    Cn = int(bias.shape[0])
+    assert tuple(w.shape) == (25, Cn) and tuple(out.shape[:3]) == (B, H, W) and out.device == x.device == w.device == bias.device, (x.shape, w.shape, out.shape)
+    call = lambda: _lib.lib().pcdm_dwconv5_silu_f32(_ptr(x), B, H, W, Cn, ldi, int(in_offset), _ptr(w), _ptr(bias), _ptr(out), int(out.shape[3]),  # noqa: E731
+                                                    int(offset), _stream(x))
+    _chk(_launch(x, call, "dwconv5_silu", 50.0 * B * H * W * Cn, (B, H, W, Cn)), "pcdm_dwconv5_silu_f32")
+    return out
+
+
+def maxpool5_f32(x: torch.Tensor, Cn: int, out: torch.Tensor, *, in_offset: int = 0, offset: int = 0) -> torch.Tensor:
+    """MaxPool2d(5, stride 1, pad 2) of the channels ``[in_offset, in_offset + Cn)`` of ``x`` NHWC fp32 into the channels ``[offset, offset + Cn)`` of
+    ``out`` (which may be ``x``: disjoint slices); include/pcdm.h: pcdm_maxpool5_f32."""
+    _c(x, torch.float32); _c(out, torch.float32)
+    B, H, W, ldi = (int(v) for v in x.shape)
+    assert tuple(out.shape[:3]) == (B, H, W) and out.device == x.device, (x.shape, out.shape)
+    call = lambda: _lib.lib().pcdm_maxpool5_f32(_ptr(x), B, H, W, int(Cn), ldi, int(in_offset), _ptr(out), int(out.shape[3]), int(offset),  # noqa: E731
+                                                _stream(x))
+    _chk(_launch(x, call, "maxpool5", 25.0 * B * H * W * Cn, (B, H, W, Cn)), "pcdm_maxpool5_f32")
+    return out
+
+
+def fc_hsigmoid_f32(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """fp32 [B, C] -> hardsigmoid(x w^T + bias) with ``w`` [C, C] (include/pcdm.h: pcdm_fc_hsigmoid_f32)."""
+    _c(x, torch.float32); _c(w, torch.float32); _c(bias, torch.float32)
+    B, Cn = (int(v) for v in x.shape)
+    assert tuple(w.shape) == (Cn, Cn) and tuple(bias.shape) == (Cn,) and w.device == x.device == bias.device, (x.shape, w.shape)
+    out = torch.empty_like(x)
+    call = lambda: _lib.lib().pcdm_fc_hsigmoid_f32(_ptr(x), B, Cn, _ptr(w), _ptr(bias), _ptr(out), _stream(x))  # noqa: E731
+    _chk(_launch(x, call, "fc_hsigmoid", 2.0 * B * Cn * Cn, (B, Cn)), "pcdm_fc_hsigmoid_f32")
+    return out
+
+
+def scalenorm_f32(x: torch.Tensor, B: int, rows: int, dim: int, strides: Sequence[int], g: torch.Tensor, *, eps: float = 1e-5,
+                  side_scale: Optional[torch.Tensor] = None) -> Union[torch.Tensor, tuple]:
+    """ScaleNorm over ``dim`` elements of each of the ``B * rows`` rows of fp32 ``x``, element i of row (b, k) at flat index ``b strides[0] + k
+    strides[1] + i strides[2]`` -> fp32 [B rows, dim rounded up to 4] (the padding columns 0); with ``side_scale`` fp32 [dim] also
+    ``x * side_scale``, fp32 [B rows, dim] (include/pcdm.h: pcdm_scalenorm_f32)."""
+    _c(x, torch.float32); _c(g, torch.float32)
+    bs, rs, es = (int(v) for v in strides)
+    if min(B, rows, dim, es) <= 0 or min(bs, rs) < 0 or (B - 1) * bs + (rows - 1) * rs + (dim - 1) * es >= x.numel():
+        raise ValueError(f"{B} x {rows} rows of {dim} elements with strides {tuple(strides)} leave a tensor of {x.numel()} elements")
+    out = torch.empty((B * rows, (dim + 3) // 4 * 4), dtype=torch.float32, device=x.device)
+    side = None
+    if side_scale is not None:
+        _c(side_scale, torch.float32)
+        assert tuple(side_scale.shape) == (dim,) and side_scale.device == x.device
+        side = torch.empty((B * rows, dim), dtype=torch.float32, device=x.device)
+    call = lambda: _lib.lib().pcdm_scalenorm_f32(_ptr(x), int(B), int(rows), int(dim), bs, rs, es, float(eps), _ptr(g), _ptr(out),  # noqa: E731
+                                                 int(out.shape[1]), _ptr(side_scale), _ptr(side), int(dim), _stream(x))
+    _chk(_launch(x, call, "scalenorm", 3.0 * B * rows * dim, (B, rows, dim)), "pcdm_scalenorm_f32")
+    return out if side is None else (out, side)
+
+
+def gau_core_f32(uv: torch.Tensor, B: int, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """uv fp32 [B T, 2 e + 128] = (u | v | base), gamma / beta fp32 [2, 128] -> fp32 [B T, e] = u * (relu(q k^T / sqrt(128))^2 v) per crop of T tokens
+    (include/pcdm.h: pcdm_gau_core_f32)."""
+    _c(uv, torch.float32); _c(gamma, torch.float32); _c(beta, torch.float32)
+    rows, ld = (int(v) for v in uv.shape)
+    e = (ld - 128) // 2
+    if B <= 0 or rows % B or e <= 0 or 2 * e + 128 != ld or tuple(gamma.shape) != (2, 128) or tuple(beta.shape) != (2, 128):
+        raise ValueError(f"uv {tuple(uv.shape)} for {B} crops, gamma {tuple(gamma.shape)}, beta {tuple(beta.shape)}")
+    T = rows // B
+    out = torch.empty((rows, e), dtype=torch.float32, device=uv.device)
+    call = lambda: _lib.lib().pcdm_gau_core_f32(_ptr(uv), int(B), T, e, _ptr(gamma), _ptr(beta), _ptr(out), _stream(uv))  # noqa: E731
+    _chk(_launch(uv, call, "gau_core", 2.0 * B * T * T * (128 + e), (B, T, e)), "pcdm_gau_core_f32")
+    return out
+
+
+def simcc_decode(logits: torch.Tensor, x_bins: int, R: int, K: int, flip_idx: Optional[torch.Tensor], boxes: torch.Tensor, size: Sequence[int]):
+    """SimCC logits fp32 [R2 K, x bins + y bins] (x first; R2 = 2 R with ``flip_idx`` int32 [K]: the flip merge) and the boxes fp32 [R, 4] ->
+    (keypoints fp32 [R, K, 2] in image pixels, scores fp32 [R, K]); ``size`` = (Hin, Win) (include/pcdm.h: pcdm_simcc_decode)."""
+    _c(logits, torch.float32); _c(boxes, torch.float32)
+    flip = flip_idx is not None
+    rows = R * K * (2 if flip else 1)
+    if R <= 0 or K <= 0 or logits.dim() != 2 or logits.shape[0] != rows or not 0 < x_bins < logits.shape[1] or tuple(boxes.shape) != (R, 4):
+        raise ValueError(f"logits {tuple(logits.shape)} ({x_bins} x bins) and boxes {tuple(boxes.shape)} for {R} boxes of {K} keypoints, flip {flip}")
+    if flip:
+        _c(flip_idx, torch.int32)
+        assert tuple(flip_idx.shape) == (K,) and flip_idx.device == logits.device
+    ld = int(logits.shape[1])
+    kp = torch.empty((R, K, 2), dtype=torch.float32, device=logits.device)
+    sc = torch.empty((R, K), dtype=torch.float32, device=logits.device)
+    call = lambda: _lib.lib().pcdm_simcc_decode(_ptr(logits), ld, int(x_bins), logits.data_ptr() + 4 * int(x_bins), ld, ld - int(x_bins), int(R),  # noqa: E731
+                                                int(K), int(flip), _ptr(flip_idx), _ptr(boxes), int(size[0]), int(size[1]), _ptr(kp), _ptr(sc),
+                                                _stream(logits))
+    _chk(_launch(logits, call, "simcc_decode", float(logits.numel()), (R, K)), "pcdm_simcc_decode")
+    return kp, sc
+
+
+def dwpose_ws_bytes(cfg: "_lib.DWPoseConfig", R: int, flip: bool) -> int:
+    """Workspace bytes of ``dwpose_forward``; -1: the library refuses the configuration."""
+    return int(_lib.lib().pcdm_dwpose_ws_bytes(C.byref(cfg), int(R), int(bool(flip))))
+
+
+def dwpose_forward(images: torch.Tensor, boxes: torch.Tensor, image_index: torch.Tensor, flip: bool, cfg: "_lib.DWPoseConfig",
+                   weights: "_lib.DWPoseWeights", ws: torch.Tensor):
+    """The whole estimator as one C call: images uint8 [N, H, W, 3], boxes fp32 [R, 4], image_index int32 [R] -> (keypoints fp32 [R, K, 2], scores
+    fp32 [R, K]) (include/pcdm.h: pcdm_dwpose_forward)."""
+    _c(images, torch.uint8); _c(boxes, torch.float32); _c(image_index, torch.int32)
+    N, H, W = (int(v) for v in images.shape[:3])
+    R = int(boxes.shape[0])
+    assert images.dim() == 4 and images.shape[3] == 3 and tuple(boxes.shape) == (R, 4) and tuple(image_index.shape) == (R,)
+    assert boxes.device == images.device == image_index.device == ws.device
+    kp = torch.empty((R, cfg.K, 2), dtype=torch.float32, device=images.device)
+    sc = torch.empty((R, cfg.K), dtype=torch.float32, device=images.device)
+    _chk(_lib.lib().pcdm_dwpose_forward(_ptr(images), N, H, W, _ptr(boxes), _ptr(image_index), R, int(bool(flip)), C.byref(cfg), C.byref(weights),
+                                        _ptr(kp), _ptr(sc), _ptr(ws), ws.numel() * ws.element_size(), _stream(images)), "pcdm_dwpose_forward")
+    return kp, sc

@@ -11,6 +11,11 @@ With ``--preprocess_device gpu`` the input side moves as well: the decoded pixel
 ``pcdms_amd.preprocess`` resizes, pastes, normalises and forms the CLIP pixels on the device -- the same bytes, so the same PNGs and best indices.
 With ``--pose_source keypoints`` the pose maps are not read as images: ``<pose name>.npz`` (keypoints, scores, size: tools/README.md) next to where
 the pose image would be is rendered on the device by ``pcdms_amd.pose.draw_pose`` -- the pixels tools/render_pose.py writes for that file.
+With ``--pose_source estimator --pose_weights CKPT`` no pose file is read at all: the pose map of each source / target IMAGE is estimated on the
+device by ``pcdms_amd.pose.estimate_pose_map`` (DWPose-l from the mmpose checkpoint CKPT; the whole image is the person box: tools/README.md).
+That map is estimated from the picture as it lies on disk with detect_resolution = image_resolution = 512 and then resized to the driver's size
+like a pose file; it is NOT the file tools/extract_pose.py writes, which follows the reference's ``single_extract_pose.py`` (the picture resized to
+1024 x 1024 first, image_resolution 1024).  A pair's maps are estimated again where the driver reads a pose file again (the grid's thumbnails).
 
 Differences, on purpose: ``--img_width`` is honoured (the reference parses it but reads ``args.img_weigh``); ``ImageProjModel_p``
 takes its sizes from the checkpoint / encoder config instead of the literals 1536 / 768 / 1024 (identical for the published
@@ -72,9 +77,13 @@ def pick_best_on_device(images: torch.Tensor, t_img: Image.Image, window=None):
     return Image.fromarray(image.cpu().numpy()), int(index.item()), [float(v) for v in scores.tolist()]
 
 
-def load_pose(path: str, source: str, device, on_device: bool):
-    """The pose map the driver reads at ``path``, not yet resized: decoded from the image file (``source`` "image") or rendered on ``device`` from
-    the keypoint file of the same name with the extension .npz ("keypoints").  A uint8 [h, w, 3] tensor on ``device`` (``on_device``) or a PIL image."""
+def load_pose(path: str, source: str, device, on_device: bool, image_path: str = None, estimator=None):
+    """The pose map the driver reads at ``path``, not yet resized: decoded from the image file (``source`` "image"), rendered on ``device`` from
+    the keypoint file of the same name with the extension .npz ("keypoints"), or estimated on ``device`` from the picture at ``image_path`` by
+    ``estimator`` ("estimator").  A uint8 [h, w, 3] tensor on ``device`` (``on_device``) or a PIL image."""
+    if source == "estimator":
+        pose = P.estimate_pose_map(estimator, torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).to(device))
+        return pose if on_device else Image.fromarray(pose.cpu().numpy())
     if source == "keypoints":
         with np.load(os.path.splitext(path)[0] + ".npz") as f:
             kp, sc, (w, h) = torch.from_numpy(f["keypoints"].astype(np.float32)), torch.from_numpy(f["scores"].astype(np.float32)), (int(v) for v in f["size"])
@@ -142,6 +151,13 @@ def inference(args, rank, select_test_datas):
     W, H = args.img_width, args.img_height
     pre_gpu = getattr(args, "preprocess_device", "host") == "gpu"
     pose_source = getattr(args, "pose_source", "image")
+    estimator = None
+    if pose_source == "estimator":
+        if not getattr(args, "pose_weights", None):
+            raise ValueError("--pose_source estimator needs --pose_weights (the mmpose DWPose-l checkpoint)")
+        estimator = P.DWPoseEstimator.from_checkpoint(args.pose_weights, input_size=tuple(getattr(args, "pose_input_size", (288, 384))),
+                                                      widen_factor=getattr(args, "pose_widen_factor", 1.0),
+                                                      deepen_factor=getattr(args, "pose_deepen_factor", 1.0))
     all_ssim = []
     start_time = time.time()
     split = args.json_path.split("/")[-1].split("_")[0]
@@ -152,15 +168,16 @@ def inference(args, rank, select_test_datas):
         t_pose_path = args.pose_path + data["target_image"].replace(".jpg", "_pose.jpg")
         t_img_dev = None
         load = lambda p: Image.open(p).convert("RGB").resize((W, H), Image.BICUBIC)  # noqa: E731
-        load_p = lambda p: load_pose(p, pose_source, device, False).resize((W, H), Image.BICUBIC)  # noqa: E731
+        pose_of = lambda p, img, dev: load_pose(p, pose_source, device, dev, img, estimator)  # noqa: E731
+        load_p = lambda p, img: pose_of(p, img, False).resize((W, H), Image.BICUBIC)  # noqa: E731
         if pre_gpu:      # decode on the host, upload the raw pixels once per image, everything else on the device (pcdms_amd/preprocess.py)
             raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
-            vae_image, st_pose_t, s_img_u8 = P.stage2_inputs(raw(s_img_path), load_pose(s_pose_path, pose_source, device, True),
-                                                            load_pose(t_pose_path, pose_source, device, True), W, H)
+            vae_image, st_pose_t, s_img_u8 = P.stage2_inputs(raw(s_img_path), pose_of(s_pose_path, s_img_path, True),
+                                                            pose_of(t_pose_path, t_img_path, True), W, H)
             t_img_dev = P.resize(raw(t_img_path), (W, H))    # also what --metrics_device gpu scores against
             pix = P.clip_pixel_values(s_img_u8)
         else:
-            s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load_p(s_pose_path), load_p(t_pose_path)
+            s_img, t_img, s_pose, t_pose = load(s_img_path), load(t_img_path), load_p(s_pose_path, s_img_path), load_p(t_pose_path, t_img_path)
             s_img_t_mask = Image.new("RGB", (2 * W, H))          # [source | black]
             s_img_t_mask.paste(s_img, (0, 0))
             st_pose = Image.new("RGB", (2 * W, H))               # [source pose | target pose]
@@ -184,7 +201,7 @@ def inference(args, rank, select_test_datas):
         if pre_gpu and not on_device:      # the host scorer and the grid take PIL images: the device's bytes, brought back
             t_img = Image.fromarray(t_img_dev.cpu().numpy())
             if not args.calculate_metrics:   # (the grid's thumbnails; the pose halves are not kept as uint8 on the device)
-                s_img, s_pose, t_pose = Image.fromarray(s_img_u8.cpu().numpy()), load_p(s_pose_path), load_p(t_pose_path)
+                s_img, s_pose, t_pose = Image.fromarray(s_img_u8.cpu().numpy()), load_p(s_pose_path, s_img_path), load_p(t_pose_path, t_img_path)
         output = pipe(height=H, width=2 * W, guidance_rescale=0.0, vae_image=vae_image, s_img_proj_f=s_img_proj_f, st_pose_f=st_pose_f,
                       pred_t_img_embed=pred_t_img_embed, num_images_per_prompt=4, guidance_scale=args.guidance_scale, generator=generator,
                       num_inference_steps=args.num_inference_steps, **({"output_type": "uint8"} if on_device else {}))
@@ -248,9 +265,14 @@ def build_parser():
     p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
                    help="where the inputs are resized, pasted, normalised and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the "
                         "reference) or gpu (pcdms_amd.preprocess, the same bytes)")
-    p.add_argument("--pose_source", choices=("image", "keypoints"), default="image",
-                   help="where the pose maps come from: image (the pose image files, as the reference) or keypoints (<pose name>.npz next to them, "
-                        "rendered on the device by pcdms_amd.pose)")
+    p.add_argument("--pose_source", choices=("image", "keypoints", "estimator"), default="image",
+                   help="where the pose maps come from: image (the pose image files, as the reference), keypoints (<pose name>.npz next to them, "
+                        "rendered on the device by pcdms_amd.pose) or estimator (estimated on the device from the source / target images with "
+                        "--pose_weights; no pose file is read)")
+    p.add_argument("--pose_weights", type=str, default=None, help="the mmpose DWPose-l checkpoint (dw-ll_ucoco_384.pth) for --pose_source estimator")
+    p.add_argument("--pose_input_size", type=int, nargs=2, default=(288, 384), metavar=("W", "H"), help="crop size of the --pose_weights network")
+    p.add_argument("--pose_widen_factor", type=float, default=1.0, help="CSPNeXt widen_factor of --pose_weights (DWPose-l: 1)")
+    p.add_argument("--pose_deepen_factor", type=float, default=1.0, help="CSPNeXt deepen_factor of --pose_weights (DWPose-l: 1)")
     p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p
