@@ -558,8 +558,8 @@ int pcdm_pose_draw(const float* keypoints, const float* scores, int M, int P, in
 int pcdm_resize_linear_u8(const void* src, int M, int Hs, int Ws, void* dst, int Hd, int Wd, pcdm_stream_t s);
 
 /* ---- The whole-body pose estimator: image + person boxes -> 133 keypoints and scores per box (what Wholebody.__call__ gets from its second
- * network, the top-down DWPose-l of mmpose: CSPNeXt-l backbone, RTMCC head, SimCC decoding).  The person detector (YOLOX-l) is NOT here: boxes come
- * from the caller.  mmpose and mmdet are not dependencies; the network is restated from its published definition below, and parity with mmpose on
+ * network, the top-down DWPose-l of mmpose: CSPNeXt-l backbone, RTMCC head, SimCC decoding).  The boxes come from the person detector below
+ * (pcdm_detect_forward) or from the caller.  mmpose and mmdet are not dependencies; the network is restated from its published definition below, and parity with mmpose on
  * the published checkpoint is NOT pinned by a test that runs by default (tests/test_dwpose.py holds a dormant pin) -- the same standing as LPIPS, FID
  * and the OpenCV rules.  Everything is fp32; activations are NHWC with channels padded to multiples of 4 (padding channels exactly 0).  The schedule
  * is one C call, pcdm_dwpose_forward, or the same launches driven from the host (pcdms_amd/pose.py: DWPoseEstimator); these are its kernels.  No atomics, no allocation, no host synchronisation, fixed
@@ -659,6 +659,93 @@ int pcdm_scalenorm_f32(const float* x, int B, int rows, int dim, int64_t batch_s
 int pcdm_gau_core_f32(const float* uv, int B, int T, int e, const float* gamma, const float* beta, float* out, pcdm_stream_t s);
 int pcdm_simcc_decode(const float* simcc_x, int x_pitch, int x_bins, const float* simcc_y, int y_pitch, int y_bins, int R, int K, int flip,
                       const int32_t* flip_idx, const float* boxes, int Hin, int Win, float* keypoints, float* scores, pcdm_stream_t s);
+
+/* ---- The person detector: image -> person boxes (what Wholebody.__call__ gets from its first network, mmdet's YOLOX-l of
+ * yolox_l_8xb8-300e_coco.py, after it keeps label 0 with score > 0.5 and applies mmpose's nms(0.7)).  mmdet, mmpose and mmcv are not dependencies;
+ * the network is restated from its published definition below, and parity with mmdet on the published checkpoint is NOT pinned by a test that
+ * runs by default (tests/test_person_detector.py holds a dormant pin) -- the same standing as DWPose, LPIPS and FID.  Everything is fp32;
+ * activations are NHWC with channels padded to multiples of 4 (padding channels exactly 0).  No atomics, no allocation, no host synchronisation,
+ * fixed orders: reruns are bit-identical and an image's result does not depend on its place in the batch.  Arguments outside the stated ranges
+ * return -1 and write nothing.
+ *
+ * Input (mmdet's test pipeline: Resize(keep_ratio), Pad(pad_to_square, 114)): with S the detector's square size (a multiple of 32, 32 .. 4096),
+ *   f = S / max(H, W) in double, (Wr, Hr) = (int(W f + 0.5), int(H f + 0.5)) (pcdm_detect_resized; -1 if a side would vanish); the image is resized
+ *   to Wr x Hr by pcdm_resize_linear_u8's rule and placed top-left in an S x S canvas that is 114 elsewhere; the scale factor is (Wr / W, Hr / H),
+ *   each rounded to fp32.  The network sees B, G, R (the reference hands mmdet a BGR array; YOLOX's preprocessor neither swaps nor normalises),
+ *   values 0 .. 255.
+ * pcdm_detect_prep: images uint8 RGB [N, H, W, 3] -> the Focus tensor fp32 [N, S/2, S/2, 12]: channel (patch p) 3 + c with the patches in the order
+ *   top-left, bottom-left, top-right, bottom-right ((dy, dx) = (0, 0), (1, 0), (0, 1), (1, 1)) and c over B, G, R.  One launch.
+ * pcdm_upsample2_nearest_f32: out[b, y, x, out_offset + c] = x[b, y / 2, x / 2, in_offset + c] for x [B, H, W, in_pitch], out [B, 2 H, 2 W,
+ *   out_pitch]; C, pitches, offsets multiples of 4.  As for pcdm_conv2d_f32_act, -1 when both are overlapping slices of one tensor given by one base
+ *   pointer and one pitch; any other aliasing (another base pointer into the same allocation, another pitch) is the caller's to avoid.
+ *
+ * The network (Conv = convolution without bias + BatchNorm(eps 1e-3) + SiLU, the BatchNorm folded on the host in fp64):
+ *   backbone (CSPDarknet P5): stem Conv 3x3 12 -> 64 on the Focus tensor.  Four stages (in, out, blocks, identity, spp) = (64, 128, 3, yes, no),
+ *   (128, 256, 9, yes, no), (256, 512, 9, yes, no), (512, 1024, 3, no, yes): Conv 3x3 s2 in -> out; with spp: Conv 1x1 out -> out/2, max-pools 5 / 9 /
+ *   13 (stride 1, same size), cat [x, p5, p9, p13], Conv 1x1 2 out -> out; then the CSP layer, mid = out / 2: main = Conv 1x1 -> mid, short = Conv 1x1
+ *   -> mid, the blocks on main (Conv 1x1 mid -> mid, Conv 3x3 mid -> mid, + block input when identity), cat (main, short), Conv 1x1 2 mid -> out.
+ *   Outputs c3, c4, c5 = stages 2, 3, 4 (256 @ S/8, 512 @ S/16, 1024 @ S/32).
+ *   neck (YOLOXPAFPN; every CSP layer has 3 blocks without identity; up2 = nearest x 2): r5 = reduce_layers.0 Conv 1x1 1024 -> 512 (c5);
+ *   t4 = top_down_blocks.0 CSP(1024 -> 512)(cat [up2(r5), c4]); r4 = reduce_layers.1 Conv 1x1 512 -> 256 (t4); p3 = top_down_blocks.1 CSP(512 ->
+ *   256)(cat [up2(r4), c3]); p4 = bottom_up_blocks.0 CSP(512 -> 512)(cat [downsamples.0 Conv 3x3 s2 256 -> 256 (p3), r4]); p5 = bottom_up_blocks.1
+ *   CSP(1024 -> 1024)(cat [downsamples.1 Conv 3x3 s2 512 -> 512 (p4), r5]); out_convs.i Conv 1x1 -> 256 on p3, p4, p5.
+ *   head, per level i: multi_level_cls_convs.i and multi_level_reg_convs.i, two Conv 3x3 256 -> 256 each; multi_level_conv_cls.i Conv2d 1x1 with bias
+ *   -> C classes on the cls branch; multi_level_conv_reg.i (-> 4) and multi_level_conv_obj.i (-> 1), Conv2d 1x1 with bias, both on the reg branch.
+ *   Two load-time merges, bit-identical per output: main_conv and short_conv run as one convolution, conv_reg and conv_obj as one.  A level's
+ *   head tensor is fp32 [N, S/stride, S/stride, 8 + C4]: reg 0 .. 3, obj 4, 5 .. 7 zero, the class logits from 8 (C4 = C rounded up to 4, padding 0).
+ *
+ * Decode and selection (YOLOXHead.predict_by_feat for one class of interest; then mmpose's nms):
+ * pcdm_detect_decode: priors in level order (stride 8, 16, 32), row-major, at (x, y) = (col, row) stride; P = 21 (S / 32)^2 an image.  Per prior,
+ *   in fp32, every operation its own: centre = pred_xy stride + (x, y); wh = exp(pred_wh) stride; box = centre -+ wh / 2; label = the first argmax
+ *   of the C class logits after sigmoid; score = sigmoid(max cls) sigmoid(obj); the box is divided by the scale factor (x by Wr / W, y by Hr / H),
+ *   BEFORE the NMS, as in mmdet.  candidates[n, i] = label == class_id and score >= 0.01 and score > score_thr.  Out: boxes fp32 [N, P, 4], scores
+ *   [N, P], labels and candidates int32 [N, P].  The reference applies its 0.5 filter after mmdet's NMS; a greedy NMS in descending score order
+ *   never lets a lower score suppress a higher one, so filtering first gives the same set.
+ * pcdm_nms_f32: one greedy pass per image over the boxes whose flags[n, i] != 0 (a NaN score is never one), in the order (score descending, index
+ *   ascending), made by counting, without atomics.  If more than max_candidates (<= 1024) are flagged, the best max_candidates are used.  In that
+ *   order a box that is still kept suppresses every later one with IoU > thr, IoU = inter / (area a + area b - inter) with `offset` added to every
+ *   width and height (mmcv's nms: offset 0; mmpose's: 1); equality keeps; a suppressed box suppresses nothing.  keep (or NULL): int32 [N, P] flags of
+ *   the first max_det kept (it must not be `flags`); out_boxes fp32 [N, max_det, 4] / out_scores [N, max_det] (both or neither; one of keep and
+ *   out_boxes must be given): the first max_det kept in order, the rows behind them 0; count int32 [N] (or NULL) = the rows written; overflow int32
+ *   [N] (or NULL) = more than max_candidates flagged, or more than max_det kept, or overflow_in[n] (int32 [N] or NULL) != 0.  1 <= max_det <=
+ *   max_candidates.  One launch, one workgroup an image; N P < 2^24.  Untuned: every flagged box reads all P scores for its rank, so the cost grows
+ *   with P times the number of flagged boxes (measured only as part of pcdm_detect_forward: profiles/yolox_bench.json).
+ * pcdm_detect_forward: prep, network, decode and the two passes -- pcdm_nms_f32(candidates, nms_thr 0.65, offset 0) then pcdm_nms_f32(its keep,
+ *   pose_nms_thr 0.7, offset 1) -- as ONE C call on one caller-owned workspace of pcdm_detect_ws_bytes(cfg, N) bytes (16-byte aligned).  Bit for bit
+ *   the per-kernel calls in the same order (pcdms_amd/pose.py: PersonDetector runs either).  Out: boxes fp32 [N, max_det, 4] (x1, y1, x2, y2 in
+ *   pixels of the image, score order, rows beyond count 0), scores [N, max_det], count and overflow int32 [N].  cfg: S; num_classes (<= 1024) and
+ *   class_id; the stem's, the four stages' and the head's channels (multiples of 8); blocks per stage and per neck CSP layer (<= 64);
+ *   max_candidates (1 .. 1024) and max_det (1 .. max_candidates); the three thresholds.  wts: HOST arrays of DEVICE pointers, conv_w / conv_b
+ *   [n_conv]: the packed convolutions (pcdm_pack_lpips_conv, BatchNorm folded) in schedule order: stem; per stage: the strided convolution, (spp:
+ *   conv1, conv2,) main_conv | short_conv as one, per block conv1 and conv2, final_conv; reduce_layers.0, top_down_blocks.0, reduce_layers.1,
+ *   top_down_blocks.1, downsamples.0, bottom_up_blocks.0, downsamples.1, bottom_up_blocks.1 (CSP layers as above), out_convs 0 .. 2; per level:
+ *   cls_convs 0, 1, conv_cls (C4 outputs, the padding rows 0), reg_convs 0, 1, conv_reg | conv_obj as one (8 outputs, rows 5 .. 7 zero).  -1 and
+ *   nothing written for a NULL pointer, a count that does not match cfg, or sizes outside the ranges above. */
+typedef struct pcdm_detect_config {
+    int32_t S;
+    int32_t num_classes, class_id;
+    int32_t stem, head;
+    int32_t out[4], blocks[4];
+    int32_t neck_blocks;
+    int32_t max_candidates, max_det;
+    float score_thr, nms_thr, pose_nms_thr;
+} pcdm_detect_config;
+typedef struct pcdm_detect_weights {
+    const float* const* conv_w;
+    const float* const* conv_b;
+    int32_t n_conv;
+} pcdm_detect_weights;
+int pcdm_detect_resized(int H, int W, int S, int* Hr, int* Wr);
+int pcdm_detect_prep(const void* images, int N, int H, int W, int S, float* out, pcdm_stream_t s);
+int pcdm_upsample2_nearest_f32(const float* x, int B, int H, int W, int C, int in_pitch, int in_offset, float* out, int out_pitch, int out_offset,
+                               pcdm_stream_t s);
+int pcdm_detect_decode(const float* head8, const float* head16, const float* head32, int N, int S, int num_classes, int class_id, float score_thr, int H,
+                       int W, float* boxes, float* scores, int32_t* labels, int32_t* candidates, pcdm_stream_t s);
+int pcdm_nms_f32(const float* boxes, const float* scores, const int32_t* flags, int N, int P, int max_candidates, int max_det, float thr, float offset,
+                 const int32_t* overflow_in, int32_t* keep, float* out_boxes, float* out_scores, int32_t* count, int32_t* overflow, pcdm_stream_t s);
+int64_t pcdm_detect_ws_bytes(const pcdm_detect_config* cfg, int N);
+int pcdm_detect_forward(const void* images, int N, int H, int W, const pcdm_detect_config* cfg, const pcdm_detect_weights* wts, float* boxes,
+                        float* scores, int32_t* count, int32_t* overflow, void* ws, int64_t ws_bytes, pcdm_stream_t s);
 
 /* ---- The UNet forward as ONE entry ("a fused unet_forward(ctx, ...)" over an opaque context).
  * Replaces Stage2_InapintUNet2DConditionModel.forward (/root/reference/src/models/stage2_inpaint_unet_2d_condition.py:579-825) for a host

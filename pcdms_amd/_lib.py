@@ -97,6 +97,20 @@ class DWPoseWeights(C.Structure):
                 ("ln_g", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("res_scale", C.c_void_p), ("flip_idx", C.c_void_p)]
 
 
+class DetectConfig(C.Structure):
+    """Mirror of ``pcdm_detect_config`` (include/pcdm.h)."""
+
+    _fields_ = [("S", C.c_int32), ("num_classes", C.c_int32), ("class_id", C.c_int32), ("stem", C.c_int32), ("head", C.c_int32), ("out", C.c_int32 * 4),
+                ("blocks", C.c_int32 * 4), ("neck_blocks", C.c_int32), ("max_candidates", C.c_int32), ("max_det", C.c_int32), ("score_thr", C.c_float),
+                ("nms_thr", C.c_float), ("pose_nms_thr", C.c_float)]
+
+
+class DetectWeights(C.Structure):
+    """Mirror of ``pcdm_detect_weights`` (include/pcdm.h)."""
+
+    _fields_ = [("conv_w", C.POINTER(C.c_void_p)), ("conv_b", C.POINTER(C.c_void_p)), ("n_conv", C.c_int32)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
 _SIGS = {
@@ -172,6 +186,13 @@ _SIGS = {
     "pcdm_simcc_decode": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P], C.c_int),
     "pcdm_dwpose_ws_bytes": ([C.POINTER(DWPoseConfig), _I, _I], _L),
     "pcdm_dwpose_forward": ([_P, _I, _I, _I, _P, _P, _I, _I, C.POINTER(DWPoseConfig), C.POINTER(DWPoseWeights), _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_detect_resized": ([_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "pcdm_detect_prep": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
+    "pcdm_upsample2_nearest_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_detect_decode": ([_P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    "pcdm_nms_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "pcdm_detect_ws_bytes": ([C.POINTER(DetectConfig), _I], _L),
+    "pcdm_detect_forward": ([_P, _I, _I, _I, C.POINTER(DetectConfig), C.POINTER(DetectWeights), _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_unet_create":([C.POINTER(UNetConfig)], _P),
     "pcdm_unet_destroy": ([_P], None),
     "pcdm_unet_last_error": ([_P], C.c_char_p),

@@ -13,19 +13,11 @@ constexpr int kPdSlots = 185;                   // per person: 17 limbs + 18 joi
 constexpr int kPdInts = 8;                      // int32 per slot: {kind, p0, p1, p2, p3, p4, colour, 0}
 constexpr int kPdMaxPersons = 32, kPdMaxSide = 4096;
 constexpr int kPdTW = 32, kPdTH = 8;            // pixel tile of pose_raster_kernel: one pixel per lane
-constexpr int kPdCoord = 1 << 20;               // integer coordinates are clamped to +-2^20 (a keypoint may be any float)
 constexpr int kPdTableInts = 360 * 2 + 20;      // pcdm_pose_tables: {C, S} of every whole degree, then the 20 hand-edge colours
 enum { PD_EMPTY = 0, PD_LIMB = 1, PD_DISC = 2, PD_LINE = 3 };
 //   PD_LIMB: {cx, cy, a, C, S}   PD_DISC: {x, y, r}   PD_LINE: {x0, y0, x1, y1}
 
 __device__ __forceinline__ uint32_t pd_rgb(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
-
-// int(v) of the reference (truncation toward zero), clamped; NaN goes to the lower bound
-__device__ __forceinline__ int pd_trunc(float v) {
-    if (!(v > -(float)kPdCoord)) return -kPdCoord;
-    if (v > (float)kPdCoord) return kPdCoord;
-    return (int)v;
-}
 
 // int(math.degrees(math.atan2(y, x))): the multiples of 45 degrees are exact by case, so that a last-bit difference between two atan2
 // implementations cannot move a truncation across a whole degree; between them no fp32 pair comes that close to one
@@ -67,24 +59,24 @@ __device__ __forceinline__ PdSlot pd_slot(const float* __restrict__ kp, const fl
         const float mX = (X0 + X1) / 2.0f, mY = (Y0 + Y1) / 2.0f;
         const float dX = X0 - X1, dY = Y0 - Y1;
         const float len = sqrtf(cv_mul(dX, dX) + cv_mul(dY, dY));
-        const int a = pd_trunc(len / 2.0f);
+        const int a = cv_trunc(len / 2.0f);
         if (a < 0) return o;                                      // (a NaN coordinate)
         int th = pd_angle(dX, dY) % 360;
         if (th < 0) th += 360;
-        o = PdSlot{PD_LIMB, pd_trunc(mY), pd_trunc(mX), a, tables[2 * th], tables[2 * th + 1], pd_rgb(kBody[i][0], kBody[i][1], kBody[i][2])};
+        o = PdSlot{PD_LIMB, cv_trunc(mY), cv_trunc(mX), a, tables[2 * th], tables[2 * th + 1], pd_rgb(kBody[i][0], kBody[i][1], kBody[i][2])};
         return o;
     }
     s -= 17 * P;
     if (s < 18 * P) {                                             // ---- body joint: a disc of radius 4, no coordinate test
         const int i = s / P, n = s - i * P;
         if (!(sc[n * 134 + i] > 0.3f)) return o;
-        o = PdSlot{PD_DISC, pd_trunc(cv_mul(cx(n, i), Wf)), pd_trunc(cv_mul(cy(n, i), Hf)), 4, 0, 0, pd_rgb(kBody[i][0], kBody[i][1], kBody[i][2])};
+        o = PdSlot{PD_DISC, cv_trunc(cv_mul(cx(n, i), Wf)), cv_trunc(cv_mul(cy(n, i), Hf)), 4, 0, 0, pd_rgb(kBody[i][0], kBody[i][1], kBody[i][2])};
         return o;
     }
     s -= 18 * P;
     // a hand or face point whose score is below 0.3 becomes (-1, -1) before it is scaled: int(-1 * W) fails the x > eps test
-    auto px = [&](int n, int j) { return pd_trunc(cv_mul(sc[n * 134 + j] < 0.3f ? -1.0f : cx(n, j), Wf)); };
-    auto py = [&](int n, int j) { return pd_trunc(cv_mul(sc[n * 134 + j] < 0.3f ? -1.0f : cy(n, j), Hf)); };
+    auto px = [&](int n, int j) { return cv_trunc(cv_mul(sc[n * 134 + j] < 0.3f ? -1.0f : cx(n, j), Wf)); };
+    auto py = [&](int n, int j) { return cv_trunc(cv_mul(sc[n * 134 + j] < 0.3f ? -1.0f : cy(n, j), Hf)); };
     if (s < 82 * P) {                                             // ---- hands
         if (!hands) return o;
         const int h = s / 41, e = s - h * 41;                     // h: the left hands of every person, then the right hands
@@ -222,26 +214,6 @@ __global__ __launch_bounds__(256) void pose_raster_kernel(const int32_t* __restr
 }
 
 // ---- cv2.resize(uint8 image, INTER_LINEAR) in OpenCV's 8-bit fixed-point form (include/pcdm.h) -----------------------------------------------
-// source index and the two 11-bit weights of output d: x axis (clamp_frac): the fraction is zeroed where the index is clamped; y axis: the two
-// rows are clamped and the fraction kept
-__device__ __forceinline__ void pd_lin_coeff(int d, double scale, int n_in, bool clamp_frac, int& s0, int& s1, int& w0, int& w1) {
-#pragma clang fp contract(off)
-    double fd = ((double)d + 0.5) * scale;
-    PCDM_CV_OPAQUE(fd);
-    float f = (float)(fd - 0.5);
-    const float fl = floorf(f);
-    int s = pd_trunc(fl);
-    f = f - fl;
-    if (clamp_frac) {
-        if (s < 0) { f = 0.0f; s = 0; }
-        if (s >= n_in - 1) { f = 0.0f; s = n_in - 1; }
-    }
-    w0 = (int)rintf((1.0f - f) * 2048.0f);
-    w1 = (int)rintf(f * 2048.0f);
-    s0 = imin(imax(s, 0), n_in - 1);
-    s1 = imin(imax(s + 1, 0), n_in - 1);
-}
-
 // dst [M, Hd, Wd, 3] <- src [M, Hs, Ws, 3]; one output pixel per lane
 __global__ __launch_bounds__(256) void resize_linear_kernel(const uint8_t* __restrict__ src, int M, int Hs, int Ws, double scale_x, double scale_y,
                                                             uint8_t* __restrict__ dst, int Hd, int Wd) {
@@ -249,8 +221,8 @@ __global__ __launch_bounds__(256) void resize_linear_kernel(const uint8_t* __res
     if (i >= (int64_t)M * Hd * Wd) return;
     const int x = (int)(i % Wd), y = (int)((i / Wd) % Hd), m = (int)(i / ((int64_t)Wd * Hd));
     int xa, xb, a0, a1, ya, yb, b0, b1;
-    pd_lin_coeff(x, scale_x, Ws, true, xa, xb, a0, a1);
-    pd_lin_coeff(y, scale_y, Hs, false, ya, yb, b0, b1);
+    cv_lin_coeff(x, scale_x, Ws, true, xa, xb, a0, a1);
+    cv_lin_coeff(y, scale_y, Hs, false, ya, yb, b0, b1);
     const uint8_t* r0 = src + ((int64_t)m * Hs + ya) * Ws * 3;
     const uint8_t* r1 = src + ((int64_t)m * Hs + yb) * Ws * 3;
 #pragma unroll

@@ -1432,3 +1432,101 @@ def dwpose_forward(images: torch.Tensor, boxes: torch.Tensor, image_index: torch
     _chk(_lib.lib().pcdm_dwpose_forward(_ptr(images), N, H, W, _ptr(boxes), _ptr(image_index), R, int(bool(flip)), C.byref(cfg), C.byref(weights),
                                         _ptr(kp), _ptr(sc), _ptr(ws), ws.numel() * ws.element_size(), _stream(images)), "pcdm_dwpose_forward")
     return kp, sc
+
+
+# ------------------------------------------------------------------------------------ person detector (pcdms_amd/pose.py: PersonDetector is the public surface)
+def detect_resized(H: int, W: int, S: int) -> tuple:
+    """(Hr, Wr) of the aspect-preserving resize into the detector's S x S canvas (include/pcdm.h: pcdm_detect_resized)."""
+    hr, wr = C.c_int(0), C.c_int(0)
+    if _lib.lib().pcdm_detect_resized(int(H), int(W), int(S), C.byref(hr), C.byref(wr)) != 0:
+        raise ValueError(f"the library refuses a {H} x {W} image for a {S} x {S} detector")
+    return hr.value, wr.value
+
+
+def detect_prep(images: torch.Tensor, S: int) -> torch.Tensor:
+    """images uint8 RGB [N, H, W, 3] -> the detector's Focus tensor fp32 [N, S/2, S/2, 12] (include/pcdm.h: pcdm_detect_prep)."""
+    _c(images, torch.uint8)
+    assert images.dim() == 4 and images.shape[3] == 3, images.shape
+    N, H, W = (int(v) for v in images.shape[:3])
+    S = int(S)
+    out = torch.empty((N, S // 2, S // 2, 12), dtype=torch.float32, device=images.device)
+    call = lambda: _lib.lib().pcdm_detect_prep(_ptr(images), N, H, W, S, _ptr(out), _stream(images))  # noqa: E731
+    _chk(_launch(images, call, "detect_prep", float(out.numel()), (N, H, W, S)), "pcdm_detect_prep")
+    return out
+
+
+def upsample2_nearest_f32(x: torch.Tensor, Cn: int, out: torch.Tensor, *, in_offset: int = 0, offset: int = 0) -> torch.Tensor:
+    """Nearest x 2 of the channels ``[in_offset, in_offset + Cn)`` of ``x`` NHWC fp32 [B, H, W, pitch] into the channels ``[offset, offset + Cn)`` of
+    ``out`` [B, 2 H, 2 W, pitch] (include/pcdm.h: pcdm_upsample2_nearest_f32)."""
+    _c(x, torch.float32); _c(out, torch.float32)
+    B, H, W, ldi = (int(v) for v in x.shape)
+    assert tuple(out.shape[:3]) == (B, 2 * H, 2 * W) and out.device == x.device, (x.shape, out.shape)
+    call = lambda: _lib.lib().pcdm_upsample2_nearest_f32(_ptr(x), B, H, W, int(Cn), ldi, int(in_offset), _ptr(out), int(out.shape[3]), int(offset),  # noqa: E731
+                                                         _stream(x))
+    _chk(_launch(x, call, "upsample2_nearest", 4.0 * B * H * W * Cn, (B, H, W, Cn)), "pcdm_upsample2_nearest_f32")
+    return out
+
+
+def detect_decode(heads: Sequence[torch.Tensor], S: int, num_classes: int, class_id: int, score_thr: float, image_size: Sequence[int]):
+    """The three head tensors fp32 [N, S/stride, S/stride, 8 + C4] -> (boxes fp32 [N, P, 4] in pixels of the ``image_size`` = (H, W) image, scores
+    [N, P], labels int32 [N, P], candidates int32 [N, P]) (include/pcdm.h: pcdm_detect_decode)."""
+    h8, h16, h32 = heads
+    S, Cn = int(S), int(num_classes)
+    N, ldh = int(h8.shape[0]), 8 + (Cn + 3) // 4 * 4
+    for h, st in zip(heads, (8, 16, 32)):
+        _c(h, torch.float32)
+        assert tuple(h.shape) == (N, S // st, S // st, ldh) and h.device == h8.device, (h.shape, (N, S // st, S // st, ldh))
+    P = 21 * (S // 32) ** 2
+    boxes = torch.empty((N, P, 4), dtype=torch.float32, device=h8.device)
+    scores = torch.empty((N, P), dtype=torch.float32, device=h8.device)
+    labels = torch.empty((N, P), dtype=torch.int32, device=h8.device)
+    cand = torch.empty((N, P), dtype=torch.int32, device=h8.device)
+    call = lambda: _lib.lib().pcdm_detect_decode(_ptr(h8), _ptr(h16), _ptr(h32), N, S, Cn, int(class_id), float(score_thr), int(image_size[0]),  # noqa: E731
+                                                 int(image_size[1]), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(cand), _stream(h8))
+    _chk(_launch(h8, call, "detect_decode", float(N * P * ldh), (N, S, Cn)), "pcdm_detect_decode")
+    return boxes, scores, labels, cand
+
+
+def nms_f32(boxes: torch.Tensor, scores: torch.Tensor, flags: torch.Tensor, *, thr: float, offset: float, max_candidates: int, max_det: int,
+            overflow_in: Optional[torch.Tensor] = None, want_keep: bool = True, want_boxes: bool = True) -> dict:
+    """One greedy NMS pass per image over the flagged boxes (include/pcdm.h: pcdm_nms_f32): boxes fp32 [N, P, 4], scores [N, P], flags int32 [N, P] ->
+    ``{"keep" int32 [N, P], "boxes" [N, max_det, 4], "scores" [N, max_det], "count" int32 [N], "overflow" int32 [N]}``."""
+    _c(boxes, torch.float32); _c(scores, torch.float32); _c(flags, torch.int32)
+    N, P = (int(v) for v in scores.shape)
+    assert tuple(boxes.shape) == (N, P, 4) and tuple(flags.shape) == (N, P) and boxes.device == scores.device == flags.device
+    dev = boxes.device
+    if overflow_in is not None:
+        _c(overflow_in, torch.int32)
+        assert tuple(overflow_in.shape) == (N,) and overflow_in.device == dev
+    if not (0 < int(max_det) <= int(max_candidates)):
+        raise ValueError(f"1 <= max_det <= max_candidates: {max_det}, {max_candidates}")
+    keep = torch.empty((N, P), dtype=torch.int32, device=dev) if want_keep else None
+    ob = torch.empty((N, int(max_det), 4), dtype=torch.float32, device=dev) if want_boxes else None
+    os_ = torch.empty((N, int(max_det)), dtype=torch.float32, device=dev) if want_boxes else None
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    overflow = torch.empty(N, dtype=torch.int32, device=dev)
+    call = lambda: _lib.lib().pcdm_nms_f32(_ptr(boxes), _ptr(scores), _ptr(flags), N, P, int(max_candidates), int(max_det), float(thr), float(offset),  # noqa: E731
+                                           _ptr(overflow_in), _ptr(keep), _ptr(ob), _ptr(os_), _ptr(count), _ptr(overflow), _stream(boxes))
+    _chk(_launch(boxes, call, "nms", float(N * P), (N, P, max_candidates, max_det)), "pcdm_nms_f32")
+    return {"keep": keep, "boxes": ob, "scores": os_, "count": count, "overflow": overflow}
+
+
+def detect_ws_bytes(cfg: "_lib.DetectConfig", N: int) -> int:
+    """Workspace bytes of ``detect_forward``; -1: the library refuses the configuration."""
+    return int(_lib.lib().pcdm_detect_ws_bytes(C.byref(cfg), int(N)))
+
+
+def detect_forward(images: torch.Tensor, cfg: "_lib.DetectConfig", weights: "_lib.DetectWeights", ws: torch.Tensor):
+    """The whole detector as one C call: images uint8 [N, H, W, 3] -> (boxes fp32 [N, max_det, 4], scores [N, max_det], count int32 [N], overflow
+    int32 [N]) (include/pcdm.h: pcdm_detect_forward)."""
+    _c(images, torch.uint8)
+    assert images.dim() == 4 and images.shape[3] == 3 and images.device == ws.device
+    N, H, W = (int(v) for v in images.shape[:3])
+    dev = images.device
+    boxes = torch.empty((N, cfg.max_det, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((N, cfg.max_det), dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    overflow = torch.empty(N, dtype=torch.int32, device=dev)
+    _chk(_lib.lib().pcdm_detect_forward(_ptr(images), N, H, W, C.byref(cfg), C.byref(weights), _ptr(boxes), _ptr(scores), _ptr(count), _ptr(overflow),
+                                        _ptr(ws), ws.numel() * ws.element_size(), _stream(images)), "pcdm_detect_forward")
+    return boxes, scores, count, overflow

@@ -7,11 +7,13 @@ resolution (pcdm_resize_linear_u8).  The result feeds ``preprocess.resize`` / ``
 
 The keypoints themselves come from ``DWPoseEstimator``: the reference's second network (the top-down whole-body DWPose-l of mmpose: CSPNeXt-l,
 RTMCC head, SimCC decoding) in exact fp32 on the device, image + person boxes -> 133 keypoints and scores per box; ``estimate_pose_map`` chains
-it with the drawing.  The person detector (YOLOX-l) is NOT part of this package: boxes come from the caller, and without boxes the box is the
-whole image -- what the reference does when its detector finds nothing (dwpose/wholebody.py:78-79), which suits frames that hold one person.
-Nor is ``controlnet_aux.util.resize_image`` (cv2 Lanczos / area resampling): the detection frame is made with ``preprocess.resize``.  mmpose and
-mmdet are not dependencies; the network is restated from its published definition (include/pcdm.h) and checked against an fp64 restatement on
-synthetic weights (tests/test_dwpose.py), so parity with mmpose on the published checkpoint is NOT pinned by a test that runs by default.
+it with the drawing.  The boxes come from ``PersonDetector``: the reference's first network (mmdet's YOLOX-l) with its label, score and NMS
+filters, image -> person boxes (``detect_people``; ``estimate_pose_map(..., detector=...)``).  Without a detector and without boxes the box is
+the whole image -- what the reference does when its detector finds nothing (dwpose/wholebody.py:78-79).  ``controlnet_aux.util.resize_image``
+(cv2 Lanczos / area resampling) is not restated: the detection frame is made with ``preprocess.resize``.  mmpose, mmdet and mmcv are not
+dependencies; both networks are restated from their published definitions (include/pcdm.h) and checked against fp64 restatements on synthetic
+weights (tests/test_dwpose.py, tests/test_person_detector.py), so parity with mmpose and mmdet on the published checkpoints is NOT pinned by a
+test that runs by default.
 
 From keypoints to integer primitives the kernels repeat the reference's operations in its order and precision.  The raster rules -- which
 pixels an ellipse, a disc and a line cover -- are this project's own integer statement of OpenCV's; OpenCV is not a dependency, and parity
@@ -418,18 +420,320 @@ class DWPoseEstimator:
     forward = __call__
 
 
+# ------------------------------------------------------------------------------------------------ the person detector
+_YOLOX_P5 = ((64, 128, 3, True, False), (128, 256, 9, True, False), (256, 512, 9, True, False), (512, 1024, 3, False, True))
+MAX_CANDIDATES = 1024                                      # the NMS kernel's limit (include/pcdm.h: pcdm_nms_f32)
+
+
+class PersonDetector:
+    """The person detector of the reference's ``DWposeDetector`` (``src/configs/yolox_l_8xb8-300e_coco.py``: mmdet ``CSPDarknet`` P5, ``YOLOXPAFPN``,
+    ``YOLOXHead``) in exact fp32 on the device, with what ``Wholebody.__call__`` does to its output: label ``class_id`` (0: person), score >
+    ``score_thr`` (0.5), then mmpose's ``nms(0.7)``.
+
+    ``detector(images_u8)`` -> ``(boxes [N, max_det, 4], scores [N, max_det], count [N], overflow [N])`` on the device, without a synchronisation:
+    boxes (x1, y1, x2, y2) in pixels of the image, in score order, rows beyond ``count`` zero; ``overflow`` is set where more than
+    ``max_candidates`` (default 512, at most 1024) priors passed the thresholds or more than ``max_det`` (default 32, what ``draw_pose`` takes)
+    boxes survived -- then the best ``max_candidates`` and the first ``max_det`` are used.  ``state_dict``: mmdet's own key names (``backbone.*``,
+    ``neck.*``, ``bbox_head.*``); ``num_batches_tracked`` and keys that start with ``ema_`` (the published v2 checkpoint carries them) are ignored,
+    anything else that is unknown or missing raises and is named.  Every BatchNorm (eps 1e-3) is folded into its convolution in fp64 and rounded
+    to fp32 once; ``main_conv`` / ``short_conv`` and ``conv_reg`` / ``conv_obj`` run as one convolution each (bit-identical per output).  A call is
+    ONE C call (pcdm_detect_forward); with the ``_taps`` test hook set the same launches are issued from here one by one and every intermediate
+    tensor is recorded -- bit for bit the same result.  The network is restated from its definition (include/pcdm.h): parity with mmdet on the
+    published checkpoint is not pinned by a test that runs by default."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, size: int = 640, widen_factor: float = 1.0, deepen_factor: float = 1.0,
+                 num_classes: int = 80, class_id: int = 0, score_thr: float = 0.5, nms_thr: float = 0.65, pose_nms_thr: float = 0.7,
+                 max_candidates: int = 512, max_det: int = MAX_PERSONS, bn_eps: float = 1e-3):
+        self.S, self.C, self.class_id = int(size), int(num_classes), int(class_id)
+        if not 32 <= self.S <= MAX_SIDE or self.S % 32:
+            raise ValueError(f"size must be a multiple of 32 (the backbone's stride) in 32 .. {MAX_SIDE}: {size}")
+        if not 0 < self.C <= 1024 or not 0 <= self.class_id < self.C:
+            raise ValueError(f"num_classes in 1 .. 1024 and class_id below it: {num_classes}, {class_id}")
+        if not 0 < int(max_det) <= int(max_candidates) <= MAX_CANDIDATES:
+            raise ValueError(f"1 <= max_det <= max_candidates <= {MAX_CANDIDATES}: {max_det}, {max_candidates}")
+        self.max_candidates, self.max_det = int(max_candidates), int(max_det)
+        self.score_thr, self.nms_thr, self.pose_nms_thr, self.bn_eps = float(score_thr), float(nms_thr), float(pose_nms_thr), float(bn_eps)
+        self.stem, self.head = int(_YOLOX_P5[0][0] * widen_factor), int(256 * widen_factor)
+        self.stages = [(int(ci * widen_factor), int(co * widen_factor), max(round(nb * deepen_factor), 1), ident, spp)
+                       for ci, co, nb, ident, spp in _YOLOX_P5]
+        self.neck_blocks = max(round(3 * deepen_factor), 1)
+        if self.stem % 8 or self.head % 8 or any(co % 8 for _, co, _, _, _ in self.stages):
+            raise ValueError(f"widen_factor {widen_factor} gives channel counts that are no multiples of 8 (branches are slices of four-channel groups)")
+        self.C4 = (self.C + 3) // 4 * 4
+        self._taps: Optional[Dict[str, torch.Tensor]] = None
+        self._dev: Dict[str, dict] = {}
+        self._host = self._pack(dict(state_dict))
+
+    # ---------------------------------------------------------------- weights
+    def _csp_layers(self) -> List[Tuple[str, int, int, int]]:
+        """every CSP layer as (module name, in, out, blocks), backbone first"""
+        _, o1, o2, o3 = (co for _, co, _, _, _ in self.stages)
+        out = [(f"backbone.stage{s}.{2 if spp else 1}", co, co, nb) for s, (_, co, nb, _, spp) in enumerate(self.stages, 1)]
+        nb = self.neck_blocks
+        return out + [("neck.top_down_blocks.0", 2 * o2, o2, nb), ("neck.top_down_blocks.1", 2 * o1, o1, nb),
+                      ("neck.bottom_up_blocks.0", 2 * o1, o2, nb), ("neck.bottom_up_blocks.1", 2 * o2, o3, nb)]
+
+    def expected_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """Every key of mmdet's state dict for this configuration (``num_batches_tracked`` and ``ema_*`` are accepted and ignored)."""
+        exp: Dict[str, Tuple[int, ...]] = {}
+
+        def cm(name, co, ci, k):
+            exp[f"{name}.conv.weight"] = (co, ci, k, k)
+            for b in _BN:
+                exp[f"{name}.bn.{b}"] = (co,)
+
+        _, o1, o2, o3 = (co for _, co, _, _, _ in self.stages)
+        cm("backbone.stem.conv", self.stem, 12, 3)
+        for s, (ci, co, _, _, spp) in enumerate(self.stages, 1):
+            cm(f"backbone.stage{s}.0", co, ci, 3)
+            if spp:
+                cm(f"backbone.stage{s}.1.conv1", co // 2, co, 1); cm(f"backbone.stage{s}.1.conv2", co, 2 * co, 1)
+        for n, ci, co, nb in self._csp_layers():
+            mid = co // 2
+            cm(f"{n}.main_conv", mid, ci, 1); cm(f"{n}.short_conv", mid, ci, 1); cm(f"{n}.final_conv", co, 2 * mid, 1)
+            for b in range(nb):
+                cm(f"{n}.blocks.{b}.conv1", mid, mid, 1); cm(f"{n}.blocks.{b}.conv2", mid, mid, 3)
+        cm("neck.reduce_layers.0", o2, o3, 1); cm("neck.reduce_layers.1", o1, o2, 1)
+        cm("neck.downsamples.0", o1, o1, 3); cm("neck.downsamples.1", o2, o2, 3)
+        for i, c in enumerate((o1, o2, o3)):
+            cm(f"neck.out_convs.{i}", self.head, c, 1)
+            for j in range(2):
+                cm(f"bbox_head.multi_level_cls_convs.{i}.{j}", self.head, self.head, 3); cm(f"bbox_head.multi_level_reg_convs.{i}.{j}", self.head, self.head, 3)
+            for t, co in (("cls", self.C), ("reg", 4), ("obj", 1)):
+                exp[f"bbox_head.multi_level_conv_{t}.{i}.weight"], exp[f"bbox_head.multi_level_conv_{t}.{i}.bias"] = (co, self.head, 1, 1), (co,)
+        return exp
+
+    def _pack(self, sd: Dict[str, torch.Tensor]) -> dict:
+        exp = self.expected_shapes()
+        sd = {k: v for k, v in sd.items() if not k.endswith(".num_batches_tracked") and not k.startswith("ema_")}
+        missing, unknown = sorted(k for k in exp if k not in sd), sorted(k for k in sd if k not in exp)
+        bad = [f"{k}: {tuple(sd[k].shape)} vs {exp[k]}" for k in exp if k in sd and tuple(sd[k].shape) != exp[k]]
+        if missing or unknown or bad:
+            raise KeyError(f"PersonDetector state dict (mmdet's key names): missing {missing[:8]}{'...' if len(missing) > 8 else ''}, "
+                           f"unknown {unknown[:8]}{'...' if len(unknown) > 8 else ''}, shape {bad[:8]}")
+        f64 = lambda k: sd[k].detach().to("cpu", torch.float64)   # noqa: E731
+
+        def folded(name):
+            g, b, m, v = (f64(f"{name}.bn.{t}") for t in _BN)
+            scale = g / torch.sqrt(v + self.bn_eps)
+            return (f64(f"{name}.conv.weight") * scale.view(-1, 1, 1, 1)).to(torch.float32), (b - m * scale).to(torch.float32)
+
+        def padded(w, b, co):   # zero rows up to co outputs: the padding channels come out exactly 0
+            return torch.cat([w, w.new_zeros((co - w.shape[0], *w.shape[1:]))]), torch.cat([b, b.new_zeros(co - b.shape[0])])
+
+        host: dict = {}
+        merged = {n for n, _, _, _ in self._csp_layers()}
+        for k in exp:
+            if not k.endswith(".conv.weight"):
+                continue
+            name = k[:-len(".conv.weight")]
+            mod, _, leaf = name.rpartition(".")
+            if mod in merged and leaf == "short_conv":
+                continue
+            w, b = folded(name)
+            if mod in merged and leaf == "main_conv":   # (main | short) as one convolution: its outputs are the concatenation
+                w2, b2 = folded(f"{mod}.short_conv")
+                w, b, name = torch.cat([w, w2]), torch.cat([b, b2]), f"{mod}.main_short"
+            host[name] = ops.pack_lpips_conv(w, b, "cpu")
+        for i in range(3):
+            f32 = lambda k: sd[k].detach().to("cpu", torch.float32)   # noqa: E731
+            pre = "bbox_head.multi_level_conv_"
+            host[f"{pre}cls.{i}"] = ops.pack_lpips_conv(*padded(f32(f"{pre}cls.{i}.weight"), f32(f"{pre}cls.{i}.bias"), self.C4), "cpu")
+            w = torch.cat([f32(f"{pre}reg.{i}.weight"), f32(f"{pre}obj.{i}.weight")])
+            b = torch.cat([f32(f"{pre}reg.{i}.bias"), f32(f"{pre}obj.{i}.bias")])
+            host[f"{pre}regobj.{i}"] = ops.pack_lpips_conv(*padded(w, b, 8), "cpu")
+        return host
+
+    @classmethod
+    def from_checkpoint(cls, path, **kwargs) -> "PersonDetector":
+        """An mmdet ``.pth`` (``{"state_dict": ...}`` or the bare state dict), read with ``weights_only=True``; ``kwargs`` as for the constructor."""
+        ck = torch.load(str(path), map_location="cpu", weights_only=True)
+        if isinstance(ck, dict) and isinstance(ck.get("state_dict"), dict):
+            ck = ck["state_dict"]
+        return cls(dict(ck), **kwargs)
+
+    def _weights(self, device: torch.device) -> dict:
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = {n: {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in p.items()} for n, p in self._host.items()}
+        return self._dev[key]
+
+    def _conv_order(self) -> List[str]:
+        """the packed convolutions by name in schedule order = pcdm_detect_weights' order (include/pcdm.h)"""
+        def csp(n, nb):
+            return [f"{n}.main_short"] + [f"{n}.blocks.{b}.conv{j}" for b in range(nb) for j in (1, 2)] + [f"{n}.final_conv"]
+        convs = ["backbone.stem.conv"]
+        for s, (_, _, nb, _, spp) in enumerate(self.stages, 1):
+            convs.append(f"backbone.stage{s}.0")
+            if spp:
+                convs += [f"backbone.stage{s}.1.conv1", f"backbone.stage{s}.1.conv2"]
+            convs += csp(f"backbone.stage{s}.{2 if spp else 1}", nb)
+        nb = self.neck_blocks
+        convs += ["neck.reduce_layers.0"] + csp("neck.top_down_blocks.0", nb) + ["neck.reduce_layers.1"] + csp("neck.top_down_blocks.1", nb)
+        convs += ["neck.downsamples.0"] + csp("neck.bottom_up_blocks.0", nb) + ["neck.downsamples.1"] + csp("neck.bottom_up_blocks.1", nb)
+        convs += [f"neck.out_convs.{i}" for i in range(3)]
+        for i in range(3):
+            for t, last in (("cls", "cls"), ("reg", "regobj")):
+                convs += [f"bbox_head.multi_level_{t}_convs.{i}.{j}" for j in range(2)] + [f"bbox_head.multi_level_conv_{last}.{i}"]
+        return convs
+
+    def _c_args(self, device: torch.device):
+        """(pcdm_detect_config, pcdm_detect_weights) for ``pcdm_detect_forward`` on ``device`` (the pointer arrays are kept alive with the weights)"""
+        w = self._weights(device)
+        if "c_args" not in w:
+            cfg = _lib.DetectConfig(S=self.S, num_classes=self.C, class_id=self.class_id, stem=self.stem, head=self.head, neck_blocks=self.neck_blocks,
+                                    max_candidates=self.max_candidates, max_det=self.max_det, score_thr=self.score_thr, nms_thr=self.nms_thr,
+                                    pose_nms_thr=self.pose_nms_thr)
+            for i, (_, co, nb, _, _) in enumerate(self.stages):
+                cfg.out[i], cfg.blocks[i] = co, nb
+            convs = self._conv_order()
+            keep = [(C.c_void_p * len(convs))(*[w[n][key].data_ptr() for n in convs]) for key in ("w", "bias")]
+            wt = _lib.DetectWeights(n_conv=len(convs))
+            wt.conv_w, wt.conv_b = (C.cast(a, C.POINTER(C.c_void_p)) for a in keep)
+            w["c_args"] = (cfg, wt, keep)
+        return w["c_args"][0], w["c_args"][1]
+
+    def _tap(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        """Test hook (tests/test_person_detector.py): with ``self._taps`` a dict, a clone of every tensor a later launch reads is recorded."""
+        if self._taps is not None:
+            self._taps[name] = t.clone()
+        return t
+
+    # ---------------------------------------------------------------- the schedule, launch by launch (pcdm_detect_forward issues the same)
+    def _csp(self, x: torch.Tensor, cin: int, in_offset: int, w: dict, n: str, tag: str, cout: int, nb: int, ident: bool, out: Optional[torch.Tensor] = None,
+             offset: int = 0) -> torch.Tensor:
+        """CSP layer ``n`` on the channels ``[in_offset, in_offset + cin)`` of ``x``: the two branches are the halves of ONE tensor (main | short)
+        written by one convolution, the blocks rewrite the main half in place, ``final_conv`` writes the channels from ``offset`` of ``out``"""
+        tap, silu, mid = self._tap, ops.CONV_ACT_SILU, cout // 2
+        assert w[f"{n}.main_short"]["cin"] == cin
+        cat = ops.conv2d_f32_act(x, w[f"{n}.main_short"], act=silu, in_offset=in_offset)
+        tap(f"{tag}.csp.in", cat)
+        for b in range(nb):
+            t = tap(f"{tag}.blocks.{b}.conv1", ops.conv2d_f32_act(cat, w[f"{n}.blocks.{b}.conv1"], act=silu))
+            ops.conv2d_f32_act(t, w[f"{n}.blocks.{b}.conv2"], pad=(1, 1), act=silu, residual=cat if ident else None, out=cat)
+            tap(f"{tag}.blocks.{b}", cat)
+        y = ops.conv2d_f32_act(cat, w[f"{n}.final_conv"], act=silu, out=out, offset=offset)
+        tap(tag, y if out is None else out[..., offset:offset + cout].contiguous())
+        return y
+
+    def _network(self, focus: torch.Tensor, w: dict) -> List[torch.Tensor]:
+        """the Focus tensor fp32 [N, S/2, S/2, 12] -> the three head tensors fp32 [N, S/stride, S/stride, 8 + C4]"""
+        tap, silu = self._tap, ops.CONV_ACT_SILU
+        N, dev = int(focus.shape[0]), focus.device
+        (_, o0, b0, _, _), (_, o1, b1, _, _), (_, o2, b2, _, _), (_, o3, b3, _, _) = self.stages
+        s8, s16, s32, nb = self.S // 8, self.S // 16, self.S // 32, self.neck_blocks
+        new = lambda s, c: torch.empty((N, s, s, c), dtype=torch.float32, device=dev)   # noqa: E731
+        td0, td1, bu0, bu1 = new(s16, 2 * o2), new(s8, 2 * o1), new(s16, 2 * o1), new(s32, 2 * o2)
+        x = tap("stem", ops.conv2d_f32_act(focus, w["backbone.stem.conv"], pad=(1, 1), act=silu))
+        x = tap("stage1.down", ops.conv2d_f32_act(x, w["backbone.stage1.0"], stride=2, pad=(1, 1), act=silu))
+        x = self._csp(x, o0, 0, w, "backbone.stage1.1", "stage1", o0, b0, True)
+        x = tap("stage2.down", ops.conv2d_f32_act(x, w["backbone.stage2.0"], stride=2, pad=(1, 1), act=silu))
+        self._csp(x, o1, 0, w, "backbone.stage2.1", "stage2", o1, b1, True, out=td1, offset=o1)                 # c3: the second half of td1
+        x = tap("stage3.down", ops.conv2d_f32_act(td1, w["backbone.stage3.0"], stride=2, pad=(1, 1), act=silu, in_offset=o1))
+        self._csp(x, o2, 0, w, "backbone.stage3.1", "stage3", o2, b2, True, out=td0, offset=o2)                 # c4: the second half of td0
+        x = tap("stage4.down", ops.conv2d_f32_act(td0, w["backbone.stage4.0"], stride=2, pad=(1, 1), act=silu, in_offset=o2))
+        spp = new(s32, 2 * o3)   # conv1 -> slice 0; the 5 / 9 / 13 pools are the 5 x 5 maximum cascaded, each into the next slice
+        ops.conv2d_f32_act(x, w["backbone.stage4.1.conv1"], act=silu, out=spp)
+        for j in range(3):
+            ops.maxpool5_f32(spp, o3 // 2, spp, in_offset=j * (o3 // 2), offset=(j + 1) * (o3 // 2))
+        tap("stage4.spp.cat", spp)
+        x = tap("stage4.spp", ops.conv2d_f32_act(spp, w["backbone.stage4.1.conv2"], act=silu))
+        c5 = self._csp(x, o3, 0, w, "backbone.stage4.2", "stage4", o3, b3, False)
+        ops.conv2d_f32_act(c5, w["neck.reduce_layers.0"], act=silu, out=bu1, offset=o2)                           # r5
+        ops.upsample2_nearest_f32(bu1, o2, td0, in_offset=o2)
+        tap("neck.td0.cat", td0)
+        t4 = self._csp(td0, 2 * o2, 0, w, "neck.top_down_blocks.0", "neck.t4", o2, nb, False)
+        ops.conv2d_f32_act(t4, w["neck.reduce_layers.1"], act=silu, out=bu0, offset=o1)                           # r4
+        ops.upsample2_nearest_f32(bu0, o1, td1, in_offset=o1)
+        tap("neck.td1.cat", td1)
+        p3 = self._csp(td1, 2 * o1, 0, w, "neck.top_down_blocks.1", "neck.p3", o1, nb, False)
+        ops.conv2d_f32_act(p3, w["neck.downsamples.0"], stride=2, pad=(1, 1), act=silu, out=bu0)
+        tap("neck.bu0.cat", bu0)
+        p4 = self._csp(bu0, 2 * o1, 0, w, "neck.bottom_up_blocks.0", "neck.p4", o2, nb, False)
+        ops.conv2d_f32_act(p4, w["neck.downsamples.1"], stride=2, pad=(1, 1), act=silu, out=bu1)
+        tap("neck.bu1.cat", bu1)
+        p5 = self._csp(bu1, 2 * o2, 0, w, "neck.bottom_up_blocks.1", "neck.p5", o3, nb, False)
+        feats = [tap(f"head.{i}.f", ops.conv2d_f32_act(p, w[f"neck.out_convs.{i}"], act=silu)) for i, p in enumerate((p3, p4, p5))]
+        heads = []
+        for i, f in enumerate(feats):
+            head = torch.empty((*f.shape[:3], 8 + self.C4), dtype=torch.float32, device=dev)
+            for t, last, off in (("cls", "cls", 8), ("reg", "regobj", 0)):
+                a = tap(f"head.{i}.{t}.0", ops.conv2d_f32_act(f, w[f"bbox_head.multi_level_{t}_convs.{i}.0"], pad=(1, 1), act=silu))
+                b = tap(f"head.{i}.{t}.1", ops.conv2d_f32_act(a, w[f"bbox_head.multi_level_{t}_convs.{i}.1"], pad=(1, 1), act=silu))
+                ops.conv2d_f32_act(b, w[f"bbox_head.multi_level_conv_{last}.{i}"], out=head, offset=off)
+            heads.append(tap(f"head.{i}", head))
+        return heads
+
+    def select(self, boxes: torch.Tensor, scores: torch.Tensor, candidates: torch.Tensor):
+        """the two greedy passes on decoded priors: mmcv's ``nms`` (IoU > ``nms_thr``, offset 0), then mmpose's over the survivors (``pose_nms_thr``,
+        +1 on every width and height) -> ``(boxes [N, max_det, 4], scores [N, max_det], count [N], overflow [N])``"""
+        first = ops.nms_f32(boxes, scores, candidates, thr=self.nms_thr, offset=0.0, max_candidates=self.max_candidates, max_det=self.max_candidates,
+                            want_boxes=False)
+        self._tap("nms.keep", first["keep"])
+        r = ops.nms_f32(boxes, scores, first["keep"], thr=self.pose_nms_thr, offset=1.0, max_candidates=self.max_candidates, max_det=self.max_det,
+                        overflow_in=first["overflow"], want_keep=self._taps is not None)
+        if self._taps is not None:
+            self._tap("nms2.keep", r["keep"])
+        return r["boxes"], r["scores"], r["count"], r["overflow"]
+
+    def __call__(self, images_u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``images_u8`` uint8 RGB ``[N, H, W, 3]`` (or one ``[H, W, 3]``) on the device."""
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() not in (3, 4) or images_u8.shape[-1] != 3:
+            raise ValueError(f"images are uint8 [N, H, W, 3] or [H, W, 3]: got {getattr(images_u8, 'dtype', type(images_u8))} "
+                             f"{tuple(getattr(images_u8, 'shape', ()))}")
+        img = (images_u8 if images_u8.dim() == 4 else images_u8.unsqueeze(0)).contiguous()
+        N, H, W = (int(v) for v in img.shape[:3])
+        if N == 0 or H == 0 or W == 0:
+            raise ValueError(f"empty images: {tuple(img.shape)}")
+        ops.detect_resized(H, W, self.S)                                       # (raises for a size the library refuses)
+        dev = img.device
+        w = self._weights(dev)
+        if self._taps is None:   # the product path: the whole schedule as one C call on one workspace
+            cfg, wt = self._c_args(dev)
+            n = ops.detect_ws_bytes(cfg, N)
+            if n < 0:
+                raise ValueError(f"the library refuses {N} images for this configuration")
+            return ops.detect_forward(img, cfg, wt, torch.empty(n // 4, dtype=torch.float32, device=dev))
+        heads = self._network(self._tap("focus", ops.detect_prep(img, self.S)), w)
+        boxes, scores, labels, cand = ops.detect_decode(heads, self.S, self.C, self.class_id, self.score_thr, (H, W))
+        for k, v in (("decode.boxes", boxes), ("decode.scores", scores), ("decode.labels", labels), ("decode.candidates", cand)):
+            self._tap(k, v)
+        return self.select(boxes, scores, cand)
+
+    forward = __call__
+
+
+def detect_people(detector: PersonDetector, images_u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(boxes [R, 4], image_index [R])`` in the form ``DWPoseEstimator.__call__`` takes: every image's detected persons in score order, and for
+    an image without a detection its whole frame (the reference's fallback, dwpose/wholebody.py:78-79).  The counts are read back from the device
+    (one small copy, one synchronisation) because R is a tensor size."""
+    img = images_u8 if images_u8.dim() == 4 else images_u8.unsqueeze(0)
+    boxes, _, count, _ = detector(img)
+    H, W = int(img.shape[1]), int(img.shape[2])
+    out, index = [], []
+    for n, c in enumerate(count.tolist()):
+        out.append(boxes[n, :c] if c else boxes.new_tensor([[0.0, 0.0, float(W), float(H)]]))
+        index += [n] * max(c, 1)
+    return torch.cat(out), torch.tensor(index, dtype=torch.int32).to(boxes.device)
+
+
 def estimate_pose_map(estimator: DWPoseEstimator, image_u8: torch.Tensor, *, detect_resolution: int = 512, image_resolution: int = 512,
-                      boxes=None, hands: bool = True, faces: bool = False, return_keypoints: bool = False):
-    """``DWposeDetector.__call__(image, detect_resolution, image_resolution)`` without the person detector: uint8 RGB ``[H, W, 3]`` on the device
-    -> the pose map uint8 ``[H', W', 3]``, (H', W') = ``detect_size(H, W, image_resolution)``.  The image is resized to the detection frame
+                      boxes=None, hands: bool = True, faces: bool = False, return_keypoints: bool = False,
+                      detector: Optional[PersonDetector] = None):
+    """``DWposeDetector.__call__(image, detect_resolution, image_resolution)``: uint8 RGB ``[H, W, 3]`` on the device -> the pose map uint8
+    ``[H', W', 3]``, (H', W') = ``detect_size(H, W, image_resolution)``.  The image is resized to the detection frame
     ``detect_size(H, W, detect_resolution)`` with ``preprocess.resize`` (Pillow bicubic; the reference's cv2 Lanczos / area resampling is not
-    restated), the estimator runs on ``boxes`` (pixels of the detection frame; None: the whole frame), and every box's person is drawn.
+    restated), the estimator runs on ``boxes`` (pixels of the detection frame), and every box's person is drawn.  ``boxes`` None: with a
+    ``detector`` they are ``detect_people(detector, frame)`` -- the reference's whole pipeline, pixels -> boxes -> keypoints -> map; without one
+    the box is the whole frame, what the reference does when its detector finds nothing.
     ``return_keypoints``: ``(map, keypoints [R, 133, 2], scores [R, 133], (Hd, Wd))`` -- what tools/extract_pose.py writes next to the image."""
     if image_u8.dim() != 3 or image_u8.dtype != torch.uint8 or image_u8.shape[2] != 3:
         raise ValueError(f"an image is uint8 [H, W, 3]: got {image_u8.dtype} {tuple(image_u8.shape)}")
     H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
     Hd, Wd = detect_size(H, W, detect_resolution)
     frame = preprocess.resize(image_u8, (Wd, Hd))
+    if boxes is None and detector is not None:
+        boxes, _ = detect_people(detector, frame)
     kp, sc = estimator(frame, boxes)
     kp134, sc134 = wholebody_to_openpose(kp, sc)
     pose_map = draw_pose(kp134, sc134, (Hd, Wd), image_size=detect_size(H, W, image_resolution), hands=hands, faces=faces)[0]
