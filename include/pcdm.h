@@ -833,6 +833,33 @@ int pcdm_pack_linear(const float* w, const float* bias, int N, int K, int pad_to
 int pcdm_pack_conv3x3(const float* w, const float* bias, int N, int Cin, int pad_to, uint16_t* out_w, float* out_bias, int* K_out, int* cin_out);
 int pcdm_pack_geglu(const float* w, const float* bias, int D, int K, uint16_t* out_w, float* out_bias);
 
+/* ---- Test / debug hooks for workspace containment (tests/test_workspace_containment.py).  Not for product code; both the product library and
+ * the lane-emulator build export them.
+ *
+ * Red zone: a process-wide byte count (default 0; a non-negative multiple of 256, anything else is refused with -1) that EVERY workspace layout
+ * computed afterwards leaves unused behind each buffer it carves out of a caller-owned workspace -- the five sub-allocators: the plan of
+ * pcdm_unet_*, and the layouts of pcdm_dwpose_forward, pcdm_detect_forward, pcdm_lpips and pcdm_inception_features.  The matching
+ * pcdm_unet_workspace_bytes / *_ws_bytes count those bytes; the cached UNet plan is keyed on the value, so changing it re-plans (and moves every
+ * buffer: conditionings prepared under another value are void).  With 0 every offset and every total is what it was without the hook.
+ * Set it BEFORE a layout is computed (before the *_ws_bytes query whose workspace a call will run on), keep it unchanged across all calls on that
+ * workspace, and RESTORE it (0) afterwards: it is not thread-safe and nothing resets it.  A test fills the zones with a byte pattern, runs the
+ * calls, and requires the pattern to be intact: a kernel that overruns its buffer by a padded row or a full-line store then shows, instead of
+ * landing silently in the next buffer of the same workspace.
+ *
+ * Layout enumerators: one per sub-allocator, with the arguments of its *_ws_bytes plus an index.  Each returns the NUMBER of entries (>= 1) and,
+ * for 0 <= index < that number, writes the buffer's name (a string owned by the library; for the UNet valid until the context re-plans or is
+ * destroyed), its byte offset in the workspace and its byte count WITHOUT the red zone (the red zone, if any, follows at offset + bytes).
+ * index = -1 only counts (the three output pointers may then be NULL; NULL outputs are skipped for any index).  Returns -1 for arguments the
+ * matching *_ws_bytes refuses and for any other index.  Entries come in offset order; pcdm_unet_workspace_layout reports the live regions of
+ * the context's plan for that shape (and, like pcdm_unet_workspace_bytes, makes it the current plan). */
+int pcdm_set_workspace_redzone(int64_t bytes);
+int64_t pcdm_get_workspace_redzone(void);
+int pcdm_unet_workspace_layout(pcdm_unet* u, int B, int h, int w, int L, int index, const char** name, int64_t* offset, int64_t* bytes);
+int pcdm_dwpose_ws_layout(const pcdm_dwpose_config* cfg, int R, int flip, int index, const char** name, int64_t* offset, int64_t* bytes);
+int pcdm_detect_ws_layout(const pcdm_detect_config* cfg, int N, int index, const char** name, int64_t* offset, int64_t* bytes);
+int pcdm_lpips_ws_layout(int N, int ref_n, int H, int W, int index, const char** name, int64_t* offset, int64_t* bytes);
+int pcdm_inception_ws_layout(int B, int H, int W, int dims, int index, const char** name, int64_t* offset, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

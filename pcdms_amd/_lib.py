@@ -113,6 +113,7 @@ class DetectWeights(C.Structure):
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _W4 = C.POINTER(C.c_int32)   # an image window {x0, y0, W, H} in host memory
+_ENT = (C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64))   # a layout entry's outputs: name, byte offset, byte count
 _SIGS = {
     "pcdm_version": ([], C.c_int),
     "pcdm_is_emulator": ([], C.c_int),
@@ -212,6 +213,14 @@ _SIGS = {
     "pcdm_pack_linear": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "pcdm_pack_conv3x3": ([_P, _P, _I, _I, _I, _P, _P, _P, _P], C.c_int),
     "pcdm_pack_geglu": ([_P, _P, _I, _I, _P, _P], C.c_int),
+    # test / debug hooks (include/pcdm.h: workspace containment): the red-zone size and one layout enumerator per sub-allocator
+    "pcdm_set_workspace_redzone": ([_L], C.c_int),
+    "pcdm_get_workspace_redzone": ([], _L),
+    "pcdm_unet_workspace_layout": ([_P, _I, _I, _I, _I, _I, *_ENT], C.c_int),
+    "pcdm_dwpose_ws_layout": ([C.POINTER(DWPoseConfig), _I, _I, _I, *_ENT], C.c_int),
+    "pcdm_detect_ws_layout": ([C.POINTER(DetectConfig), _I, _I, *_ENT], C.c_int),
+    "pcdm_lpips_ws_layout": ([_I, _I, _I, _I, _I, *_ENT], C.c_int),
+    "pcdm_inception_ws_layout": ([_I, _I, _I, _I, _I, *_ENT], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

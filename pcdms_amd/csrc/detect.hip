@@ -255,6 +255,8 @@ struct DetLayout {
     // byte offsets: the Focus tensor | x0, x1 (the backbone's running tensor) | cat, t (a CSP layer's concatenation and block intermediate) | spp |
     // the neck's four concatenations | c5, t4, p3, p4, p5 | the out_convs' maps | a head branch's two intermediates | the head tensors | decode, NMS
     int64_t focus, x[2], cat, t, spp, td0, td1, bu0, bu1, c5, t4, p3, p4, p5, f[3], hb[2], head[3], box, score, label, cand, keep, ovf, total;
+    struct { const char* name; int64_t off, bytes; } ent[29];   // every buffer in offset order (pcdm_detect_ws_layout)
+    int n_ent;
 };
 inline int64_t det_align(int64_t elems) { return (elems * (int64_t)sizeof(float) + 255) / 256 * 256; }
 inline bool detect_cfg_ok(const pcdm_detect_config* c) {
@@ -283,17 +285,25 @@ inline bool detect_layout(const pcdm_detect_config* c, int N, DetLayout* o) {
         p8 * ldh >= (int64_t)1 << 31 || p8 * c->head >= (int64_t)1 << 31 || B * P >= (int64_t)1 << 24)
         return false;
     int64_t at = 0;
-    auto take = [&](int64_t elems) { const int64_t here = at; at += det_align(elems); return here; };
-    o->focus = take(p2 * 12);
-    o->x[0] = take(x); o->x[1] = take(x);
-    o->cat = take(cat); o->t = take((cat + 1) / 2);
-    o->spp = take(p32 * 2 * o3);
-    o->td0 = take(p16 * 2 * o2); o->td1 = take(p8 * 2 * o1); o->bu0 = take(p16 * 2 * o1); o->bu1 = take(p32 * 2 * o2);
-    o->c5 = take(p32 * o3); o->t4 = take(p16 * o2); o->p3 = take(p8 * o1); o->p4 = take(p16 * o2); o->p5 = take(p32 * o3);
-    o->f[0] = take(p8 * c->head); o->f[1] = take(p16 * c->head); o->f[2] = take(p32 * c->head);
-    o->hb[0] = take(p8 * c->head); o->hb[1] = take(p8 * c->head);
-    o->head[0] = take(p8 * ldh); o->head[1] = take(p16 * ldh); o->head[2] = take(p32 * ldh);
-    o->box = take(B * P * 4); o->score = take(B * P); o->label = take(B * P); o->cand = take(B * P); o->keep = take(B * P); o->ovf = take(B);
+    const int64_t redzone = pcdm_get_workspace_redzone();   // (test hook: bytes left unused behind every buffer; 0 in product use)
+    o->n_ent = 0;
+    auto take = [&](const char* name, int64_t elems) {
+        const int64_t here = at;
+        o->ent[o->n_ent++] = {name, here, det_align(elems)};
+        at += det_align(elems) + redzone;
+        return here;
+    };
+    o->focus = take("focus", p2 * 12);
+    o->x[0] = take("x0", x); o->x[1] = take("x1", x);
+    o->cat = take("cat", cat); o->t = take("t", (cat + 1) / 2);
+    o->spp = take("spp", p32 * 2 * o3);
+    o->td0 = take("td0", p16 * 2 * o2); o->td1 = take("td1", p8 * 2 * o1); o->bu0 = take("bu0", p16 * 2 * o1); o->bu1 = take("bu1", p32 * 2 * o2);
+    o->c5 = take("c5", p32 * o3); o->t4 = take("t4", p16 * o2); o->p3 = take("p3", p8 * o1); o->p4 = take("p4", p16 * o2); o->p5 = take("p5", p32 * o3);
+    o->f[0] = take("f0", p8 * c->head); o->f[1] = take("f1", p16 * c->head); o->f[2] = take("f2", p32 * c->head);
+    o->hb[0] = take("hb0", p8 * c->head); o->hb[1] = take("hb1", p8 * c->head);
+    o->head[0] = take("head0", p8 * ldh); o->head[1] = take("head1", p16 * ldh); o->head[2] = take("head2", p32 * ldh);
+    o->box = take("box", B * P * 4); o->score = take("score", B * P); o->label = take("label", B * P); o->cand = take("cand", B * P);
+    o->keep = take("keep", B * P); o->ovf = take("ovf", B);
     o->total = at;
     return true;
 }
@@ -302,6 +312,17 @@ inline bool detect_layout(const pcdm_detect_config* c, int N, DetLayout* o) {
 extern "C" int64_t pcdm_detect_ws_bytes(const pcdm_detect_config* cfg, int N) {
     DetLayout lay;
     return detect_layout(cfg, N, &lay) ? lay.total : -1;
+}
+
+extern "C" int pcdm_detect_ws_layout(const pcdm_detect_config* cfg, int N, int index, const char** name, int64_t* offset, int64_t* bytes) {
+    DetLayout lay;
+    if (!detect_layout(cfg, N, &lay)) return -1;
+    if (index == -1) return lay.n_ent;
+    if (index < 0 || index >= lay.n_ent) return -1;
+    if (name) *name = lay.ent[index].name;
+    if (offset) *offset = lay.ent[index].off;
+    if (bytes) *bytes = lay.ent[index].bytes;
+    return lay.n_ent;
 }
 
 extern "C" int pcdm_detect_forward(const void* images, int N, int H, int W, const pcdm_detect_config* cfg, const pcdm_detect_weights* wts, float* boxes,

@@ -247,15 +247,29 @@ inline bool lpips_geom(int H, int W, LpGeom* g) {
 }
 inline int64_t lp_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
 // workspace: [input B H W 4 | tap 1..5 | pool 1, 2 | partials 5 N kLpSlices fp64], each a multiple of 256 bytes; offsets in bytes
-struct LpLayout { int64_t in, tap[5], pool[2], part, total; };
+struct LpLayout {
+    int64_t in, tap[5], pool[2], part, total;
+    struct { const char* name; int64_t off, bytes; } ent[9];   // every buffer in offset order (pcdm_lpips_ws_layout)
+    int n_ent;
+};
 inline LpLayout lpips_layout(int N, int ref_n, int H, int W, const LpGeom& g) {
+    static const char* const kTap[5] = {"tap0", "tap1", "tap2", "tap3", "tap4"};
+    static const char* const kPool[2] = {"pool0", "pool1"};
     const int64_t B = N + ref_n;
     LpLayout o;
     int64_t at = 0;
-    o.in = at;  at += lp_align(B * H * W * 4 * (int64_t)sizeof(float));
-    for (int l = 0; l < 5; ++l) { o.tap[l] = at; at += lp_align(B * g.h[l] * g.w[l] * kLpChan[l] * (int64_t)sizeof(float)); }
-    for (int i = 0; i < 2; ++i) { o.pool[i] = at; at += lp_align(B * g.hp[i] * g.wp[i] * kLpChan[i] * (int64_t)sizeof(float)); }
-    o.part = at; at += lp_align((int64_t)5 * N * kLpSlices * (int64_t)sizeof(double));
+    const int64_t redzone = pcdm_get_workspace_redzone();   // (test hook: bytes left unused behind every buffer; 0 in product use)
+    o.n_ent = 0;
+    auto take = [&](const char* name, int64_t bytes) {
+        const int64_t here = at;
+        o.ent[o.n_ent++] = {name, here, lp_align(bytes)};
+        at += lp_align(bytes) + redzone;
+        return here;
+    };
+    o.in = take("in", B * H * W * 4 * (int64_t)sizeof(float));
+    for (int l = 0; l < 5; ++l) o.tap[l] = take(kTap[l], B * g.h[l] * g.w[l] * kLpChan[l] * (int64_t)sizeof(float));
+    for (int i = 0; i < 2; ++i) o.pool[i] = take(kPool[i], B * g.hp[i] * g.wp[i] * kLpChan[i] * (int64_t)sizeof(float));
+    o.part = take("part", (int64_t)5 * N * kLpSlices * (int64_t)sizeof(double));
     o.total = at;
     return o;
 }
@@ -369,6 +383,18 @@ extern "C" int64_t pcdm_lpips_ws_bytes(int N, int ref_n, int H, int W) {
     LpGeom g;
     if (!lpips_sizes_ok(N, ref_n, H, W) || !lpips_geom(H, W, &g)) return -1;
     return lpips_layout(N, ref_n, H, W, g).total;
+}
+
+extern "C" int pcdm_lpips_ws_layout(int N, int ref_n, int H, int W, int index, const char** name, int64_t* offset, int64_t* bytes) {
+    LpGeom g;
+    if (!lpips_sizes_ok(N, ref_n, H, W) || !lpips_geom(H, W, &g)) return -1;
+    const LpLayout lay = lpips_layout(N, ref_n, H, W, g);
+    if (index == -1) return lay.n_ent;
+    if (index < 0 || index >= lay.n_ent) return -1;
+    if (name) *name = lay.ent[index].name;
+    if (offset) *offset = lay.ent[index].off;
+    if (bytes) *bytes = lay.ent[index].bytes;
+    return lay.n_ent;
 }
 
 extern "C" int pcdm_lpips(const void* img0, int N, int H0, int W0, const int32_t* win0, const void* img1, int ref_n, int H1, int W1,
@@ -704,11 +730,16 @@ inline bool inception_plan(int H, int W, int dims, IncPlan* p) {
 }
 inline bool inception_sizes_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (int64_t)1 << 27; }
 // workspace: the six buffers in enum order, each a multiple of 256 bytes; offsets in bytes
-struct IncLayout { int64_t at[kIncBufs], total; };
+struct IncLayout { int64_t at[kIncBufs], bytes[kIncBufs], total; };
 inline IncLayout inception_layout(int B, const IncPlan& p) {
     IncLayout o;
     int64_t at = 0;
-    for (int i = 0; i < kIncBufs; ++i) { o.at[i] = at; at += lp_align((int64_t)B * p.elems[i] * (int64_t)sizeof(float)); }
+    const int64_t redzone = pcdm_get_workspace_redzone();   // (test hook: bytes left unused behind every buffer; 0 in product use)
+    for (int i = 0; i < kIncBufs; ++i) {
+        o.at[i] = at;
+        o.bytes[i] = lp_align((int64_t)B * p.elems[i] * (int64_t)sizeof(float));
+        at += o.bytes[i] + redzone;
+    }
     o.total = at;
     return o;
 }
@@ -731,6 +762,19 @@ extern "C" int64_t pcdm_inception_ws_bytes(int B, int H, int W, int dims) {
     IncPlan p;
     if (!inception_sizes_ok(B, H, W) || !inception_plan(H, W, dims, &p)) return -1;
     return inception_layout(B, p).total;
+}
+
+extern "C" int pcdm_inception_ws_layout(int B, int H, int W, int dims, int index, const char** name, int64_t* offset, int64_t* bytes) {
+    static const char* const kNames[kIncBufs] = {"x", "a", "b", "t", "u", "p"};   // enum order: the input, the ping-pong pair, a block's three intermediates
+    IncPlan p;
+    if (!inception_sizes_ok(B, H, W) || !inception_plan(H, W, dims, &p)) return -1;
+    if (index == -1) return kIncBufs;
+    if (index < 0 || index >= kIncBufs) return -1;
+    const IncLayout lay = inception_layout(B, p);
+    if (name) *name = kNames[index];
+    if (offset) *offset = lay.at[index];
+    if (bytes) *bytes = lay.bytes[index];
+    return kIncBufs;
 }
 
 extern "C" int pcdm_inception_features(const void* img, int N, int Hi, int Wi, const int32_t* win, int is_f32, int resize, int normalize, int dims,

@@ -349,6 +349,8 @@ constexpr int kDwHidden = 256, kDwE = 512;                      // RTMCCHead: hi
 struct DwLayout {
     // byte offsets: crops | x0, x1 (the running tensor, ping-pong) | cat | t, u (a block's intermediates) | pool, att | the head's tensors
     int64_t crop, x[2], cat, t, u, pool, att, f, tok, x1, hn, sc, uv, core, x2, logits, total;
+    struct { const char* name; int64_t off, bytes; } ent[17];   // every buffer in offset order (pcdm_dwpose_ws_layout)
+    int n_ent;
 };
 inline int64_t dw_align(int64_t elems) { return (elems * (int64_t)sizeof(float) + 255) / 256 * 256; }
 inline bool dwpose_cfg_ok(const pcdm_dwpose_config* c) {
@@ -374,15 +376,22 @@ inline bool dwpose_layout(const pcdm_dwpose_config* c, int R, int flip, DwLayout
     const int64_t P = h * w, rows = B * c->K, bins = 2 * (int64_t)c->Win + 2 * (int64_t)c->Hin;
     if (x >= (int64_t)1 << 31 || cat >= (int64_t)1 << 31 || B * c->Hin * c->Win * 4 >= (int64_t)1 << 31 || rows * bins >= (int64_t)1 << 31) return false;
     int64_t at = 0;
-    auto take = [&](int64_t elems) { const int64_t here = at; at += dw_align(elems); return here; };
-    o->crop = take(B * c->Hin * c->Win * 4);
-    o->x[0] = take(x); o->x[1] = take(x);
-    o->cat = take(cat); o->t = take(t); o->u = take(t);
-    o->pool = take(B * cmax); o->att = take(B * cmax);
-    o->f = take(B * P * c->K); o->tok = take(rows * ((P + 3) / 4 * 4));
-    o->x1 = take(rows * kDwHidden); o->hn = take(rows * kDwHidden); o->sc = take(rows * kDwHidden);
-    o->uv = take(rows * (2 * kDwE + kGauS)); o->core = take(rows * kDwE); o->x2 = take(rows * kDwHidden);
-    o->logits = take(rows * bins);
+    const int64_t redzone = pcdm_get_workspace_redzone();   // (test hook: bytes left unused behind every buffer; 0 in product use)
+    o->n_ent = 0;
+    auto take = [&](const char* name, int64_t elems) {
+        const int64_t here = at;
+        o->ent[o->n_ent++] = {name, here, dw_align(elems)};
+        at += dw_align(elems) + redzone;
+        return here;
+    };
+    o->crop = take("crop", B * c->Hin * c->Win * 4);
+    o->x[0] = take("x0", x); o->x[1] = take("x1", x);
+    o->cat = take("cat", cat); o->t = take("t", t); o->u = take("u", t);
+    o->pool = take("pool", B * cmax); o->att = take("att", B * cmax);
+    o->f = take("f", B * P * c->K); o->tok = take("tok", rows * ((P + 3) / 4 * 4));
+    o->x1 = take("head.x1", rows * kDwHidden); o->hn = take("head.hn", rows * kDwHidden); o->sc = take("head.sc", rows * kDwHidden);
+    o->uv = take("head.uv", rows * (2 * kDwE + kGauS)); o->core = take("head.core", rows * kDwE); o->x2 = take("head.x2", rows * kDwHidden);
+    o->logits = take("logits", rows * bins);
     o->total = at;
     return true;
 }
@@ -391,6 +400,17 @@ inline bool dwpose_layout(const pcdm_dwpose_config* c, int R, int flip, DwLayout
 extern "C" int64_t pcdm_dwpose_ws_bytes(const pcdm_dwpose_config* cfg, int R, int flip) {
     DwLayout lay;
     return dwpose_layout(cfg, R, flip, &lay) ? lay.total : -1;
+}
+
+extern "C" int pcdm_dwpose_ws_layout(const pcdm_dwpose_config* cfg, int R, int flip, int index, const char** name, int64_t* offset, int64_t* bytes) {
+    DwLayout lay;
+    if (!dwpose_layout(cfg, R, flip, &lay)) return -1;
+    if (index == -1) return lay.n_ent;
+    if (index < 0 || index >= lay.n_ent) return -1;
+    if (name) *name = lay.ent[index].name;
+    if (offset) *offset = lay.ent[index].off;
+    if (bytes) *bytes = lay.ent[index].bytes;
+    return lay.n_ent;
 }
 
 extern "C" int pcdm_dwpose_forward(const void* images, int N, int H, int W, const float* boxes, const int32_t* image_index, int R, int flip,

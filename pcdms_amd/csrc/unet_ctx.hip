@@ -44,8 +44,9 @@ struct pcdm_unet {
     std::map<std::string, Vec> v;
     std::map<TileKey, std::pair<int, int>> tiles;
     // plan (valid for plan_key)
-    std::tuple<int, int, int, int> plan_key{0, 0, 0, 0};
+    std::tuple<int, int, int, int, int64_t> plan_key{0, 0, 0, 0, 0};   // B, h, w, L, the red-zone size it was laid out with
     std::map<std::string, Buf> bufs;
+    std::vector<std::string> order;   // the names of bufs in offset order (pcdm_unet_workspace_layout)
     int64_t ws_bytes = 0;
     // per WORKSPACE: what the last prepare_conditioning on it was given -- the shape, n0 = leading batch entries with an all-zero context, pose_b.
     // forward() takes n0 from the workspace it runs on (a host may alternate workspaces / batch shapes on one context) and refuses a
@@ -65,6 +66,8 @@ namespace {
 constexpr int64_t kAlign = 256;
 constexpr int64_t kSplitKFloats = 1 << 24;   // split-K workspace (fp32), as pcdms_amd.ops._splitk_ws
 
+int64_t g_redzone = 0;   // pcdm_set_workspace_redzone: bytes left unused behind every buffer a layout carves (test hook, include/pcdm.h)
+
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 bool getenv_off(const char* name) {   // A/B switches shared with pcdms_amd.ops ("0" = off)
     const char* e = getenv(name);
@@ -82,8 +85,9 @@ struct Planner {
         Buf b;
         b.off = off;
         b.bytes = round_up(bytes, kAlign);
-        off += b.bytes;
+        off += b.bytes + g_redzone;
         u->bufs[name] = b;
+        u->order.push_back(name);
     }
 };
 
@@ -347,10 +351,11 @@ std::vector<std::tuple<std::string, int, int>> transformers(const pcdm_unet_conf
 }
 
 int make_plan(pcdm_unet* u, int B, int h, int w, int L) {
-    const auto key = std::make_tuple(B, h, w, L);
+    const auto key = std::make_tuple(B, h, w, L, g_redzone);
     if (u->plan_key == key && !u->bufs.empty()) return 0;
     const pcdm_unet_config& c = u->cfg;
     u->bufs.clear();
+    u->order.clear();
     Planner P{u};
     const int n = c.n_levels;
     const int C0 = c.block_out_channels[0], temb_dim = 4 * C0;
@@ -426,11 +431,26 @@ int make_plan(pcdm_unet* u, int B, int h, int w, int L) {
             }
         }
     }
+    {   // the live regions in offset order (a name laid out twice keeps its last region only: Planner::add)
+        std::vector<std::string> live;
+        for (auto it = u->order.rbegin(); it != u->order.rend(); ++it)
+            if (std::find(live.begin(), live.end(), *it) == live.end()) live.push_back(*it);
+        std::sort(live.begin(), live.end(), [&](const std::string& a, const std::string& b) { return u->bufs[a].off < u->bufs[b].off; });
+        u->order.swap(live);
+    }
     u->ws_bytes = P.off;
     u->plan_key = key;
     return 0;
 }
 }  // namespace
+
+extern "C" int pcdm_set_workspace_redzone(int64_t bytes) {
+    if (bytes < 0 || bytes % kAlign) return -1;
+    g_redzone = bytes;
+    return 0;
+}
+
+extern "C" int64_t pcdm_get_workspace_redzone(void) { return g_redzone; }
 
 extern "C" pcdm_unet* pcdm_unet_create(const pcdm_unet_config* cfg) {
     if (!cfg || cfg->n_levels < 1 || cfg->n_levels > 8 || cfg->layers_per_block < 1) return nullptr;
@@ -508,6 +528,18 @@ extern "C" int64_t pcdm_unet_workspace_bytes(pcdm_unet* u, int B, int h, int w, 
     if (!u || B <= 0 || h <= 0 || w <= 0 || L <= 0) return -1;
     if (make_plan(u, B, h, w, L)) return -1;
     return u->ws_bytes;
+}
+
+extern "C" int pcdm_unet_workspace_layout(pcdm_unet* u, int B, int h, int w, int L, int index, const char** name, int64_t* offset, int64_t* bytes) {
+    if (!u || B <= 0 || h <= 0 || w <= 0 || L <= 0 || make_plan(u, B, h, w, L)) return -1;
+    const int n = (int)u->order.size();
+    if (index == -1) return n;
+    if (index < 0 || index >= n) return -1;
+    const auto it = u->bufs.find(u->order[index]);
+    if (name) *name = it->first.c_str();
+    if (offset) *offset = it->second.off;
+    if (bytes) *bytes = it->second.bytes;
+    return n;
 }
 
 // Zero the regions that must start at zero (GroupNorm arrival counters, the padding columns of the V^T buffers); once per workspace.
