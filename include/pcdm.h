@@ -261,6 +261,11 @@ int pcdm_small_linear(const float* x, const void* w, const float* bias, const fl
  *   M = n * B rows.  Same per-row arithmetic as the per-step launches (bit-identical results). */
 int pcdm_timestep_embedding_rows(const int64_t* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s);
 int pcdm_time_class_combine(const float* emb_t, const float* cls, void* out_bf16, int n, int B, int D, pcdm_stream_t s);
+/* float32-timestep forms (the fractional timesteps of the sigma-space samplers with timestep_spacing="linspace", e.g. 749.25): the SAME kernels
+ * instantiated for a float table; the timestep is used as the fp32 value it is, so an integer-valued float gives the bits of the int64 form. */
+int pcdm_timestep_embedding_f32(const float* t_dev, const int32_t* step_dev, float* out, int B, int dim,
+                                int flip_sin_to_cos, float shift, pcdm_stream_t s);
+int pcdm_timestep_embedding_rows_f32(const float* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s);
 
 /* ---- P-2 input assembly: cat([cat([latents]*2), mask, masked_latents], 1) (stage2_inpaint_pipeline.py:499-501)
  * -> NHWC bf16 [Bout, h, w, cpad] with channels >= 9 zero.  latents fp32 NCHW [N,4,h,w]; Bout = rep*N rows
@@ -268,6 +273,15 @@ int pcdm_time_class_combine(const float* emb_t, const float* cls, void* out_bf16
  * mask == NULL: the 8-channel stage-3 input cat([latents, gen_t_img_latents], 1) (stage3_refined_pipeline.py:538). */
 int pcdm_assemble_input(const float* latents, int N, int rep, const float* mask, int mask_b, const float* masked,
                         int masked_b, void* out, int h, int w, int cpad, pcdm_stream_t s);
+/* The same with scheduler.scale_model_input folded in (stage2_inpaint_pipeline.py:500): scale_tab != NULL multiplies the four LATENT channels
+ * by the fp32 scalar scale_tab[row * scale_stride + scale_col] of a DEVICE table of scale_rows rows -- one fp32 multiply, then the one rounding
+ * to bf16; mask, masked-latent and padding channels are untouched.  row = step_dev ? *step_dev : 0, bounded on the device: a counter outside
+ * [0, scale_rows) reads the nearest valid row and sets *step_error (may be NULL) to 1.  scale_tab == NULL: pcdm_assemble_input, bit for bit.
+ * For the pcdm_multistep_step table: scale_stride = PCDM_MS_ROW, scale_col = PCDM_MS_IN_SCALE.  Returns -1 without launching for what
+ * pcdm_assemble_input refuses, h or w < 1, and with a table: scale_rows < 1, scale_col outside [0, scale_stride), a step_error not 4-byte aligned. */
+int pcdm_assemble_input_ex(const float* latents, int N, int rep, const float* mask, int mask_b, const float* masked,
+                           int masked_b, void* out, int h, int w, int cpad, const float* scale_tab, int scale_stride, int scale_col,
+                           int scale_rows, const int32_t* step_dev, int32_t* step_error, pcdm_stream_t s);
 /* NCHW fp32 -> NHWC bf16 (pose feature st_pose_f, ref :430-431) and back.  y 16-byte aligned for the first (8-channel stores).  Both return -1
  * without launching for a NULL pointer or B, C or HW < 1; the first also for Cpad < C or Cpad % 8 != 0. */
 int pcdm_nchw_f32_to_nhwc_bf16(const float* x, void* y, int B, int C, int Cpad, int HW, pcdm_stream_t s); /* y [B,HW,Cpad], c >= C zero */
@@ -296,6 +310,33 @@ int pcdm_unipc_step(const float* eps, int cfg, float g, float* x, float* m1, flo
  * p_z != 0 (the term is then skipped).  step_dev NULL: row 0. */
 int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, float* m1, const float* noise_all, const float* coef,
                     const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+/* CFG combine + one step of EulerDiscreteScheduler / EulerAncestralDiscreteScheduler / LMSDiscreteScheduler / PNDMScheduler (PLMS) as one
+ * kernel on static state, replayable from a hipGraph: the four are linear maps on (x, a saved sample, eps and up to three older eps, noise)
+ * with host-known scalars.  State, all fp32 [n], distinct buffers, zeroed before step 0: x, xs (saved sample), h1 / h2 / h3 (eps history,
+ * h1 newest).  Row `row` of the DEVICE table coef[rows][PCDM_MS_ROW]:
+ *   {c_x, c_s, c_0, c_1, c_2, c_3, c_z, in_scale, save, push, 0, 0}
+ *   e  = eps_guided (cfg: fma(g, eps_cond - eps_uncond, eps_uncond))
+ *   x' = c_x x + c_s xs + c_0 e + c_1 h1 + c_2 h2 + c_3 h3 + c_z noise_all[row][i]
+ *   save != 0: xs <- x (the OLD x);  push != 0: h3 <- h2, h2 <- h1, h1 <- e;  x <- x'
+ * Arithmetic: the product c_x x, then FUSED multiply-adds (one rounding each) in exactly the order written, on the GPU and in the lane emulator
+ * alike.  The noise term is skipped when noise_all (fp32 [rows, n]) is NULL or the row's c_z is 0.  in_scale is not read here: it is the
+ * per-step input scale of pcdm_assemble_input_ex, kept in the same row.  row = step_dev ? *step_dev : 0, bounded on the device: a counter
+ * outside [0, rows) uses the nearest valid row and sets *step_error (may be NULL) to 1.  One element per lane, no atomics; 16-byte accesses
+ * where the addresses allow plus a scalar tail.  Returns -1 without launching for a NULL eps / state / coef pointer, rows < 1, n < 1 or a
+ * step_error that is not 4-byte aligned. */
+#define PCDM_MS_ROW 12
+#define PCDM_MS_CX 0
+#define PCDM_MS_CS 1
+#define PCDM_MS_C0 2
+#define PCDM_MS_C1 3
+#define PCDM_MS_C2 4
+#define PCDM_MS_C3 5
+#define PCDM_MS_CZ 6
+#define PCDM_MS_IN_SCALE 7
+#define PCDM_MS_SAVE 8
+#define PCDM_MS_PUSH 9
+int pcdm_multistep_step(const float* eps, int cfg, float g, float* x, float* xs, float* h1, float* h2, float* h3, const float* noise_all,
+                        const float* coef, int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s);
 /* Stage-1 prior: CFG combine (src/pipelines/stage1_prior_pipeline.py:467-471) + diffusers
  * UnCLIPScheduler.step (:478-483) + optional affine read-out (post_process_latents, stage1_prior_transformer.py:299-301).
  * pred [2N or N, n/N] fp32 (uncond rows first); HOST coefficients c8 = {p_x, p_e, clip, c_x0, c_x, c_noise, out_scale,
@@ -816,10 +857,15 @@ int pcdm_unet_set_shared_cfg_input(pcdm_unet* u, void* workspace, int shared);
  * device (clamped into the table, error flag: pcdm_unet_step_overflow). */
 int64_t pcdm_unet_time_table_bytes(const pcdm_unet* u, int n, int B);
 int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, int n, void* table, void* workspace, pcdm_stream_t s);
+/* The float32-timestep forms of pcdm_unet_prepare_timesteps / pcdm_unet_forward (t_dev is a float table: fractional timesteps); everything
+ * else as the int64 forms, and the same bits for integer-valued floats. */
+int pcdm_unet_prepare_timesteps_f32(pcdm_unet* u, const float* t_dev, int n, void* table, void* workspace, pcdm_stream_t s);
 /* x_in NHWC bf16 [B, h, w, conv_in.cin] (pcdm_assemble_input / pcdm_nchw_f32_to_nhwc_bf16); timestep = t_dev[step_dev ? *step_dev : 0] (device);
  * pose_b as passed to prepare_conditioning (0: no pose); eps_out fp32 NCHW [B, out_channels, h, w] */
 int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* t_dev, const int32_t* step_dev, int B, int h, int w, int L, int pose_b,
                       void* workspace, float* eps_out, pcdm_stream_t s);
+int pcdm_unet_forward_f32(pcdm_unet* u, const void* x_in, const float* t_dev, const int32_t* step_dev, int B, int h, int w, int L, int pose_b,
+                          void* workspace, float* eps_out, pcdm_stream_t s);
 /* Did a pcdm_unet_forward on this workspace ever find *step_dev outside the time table of pcdm_unet_prepare_timesteps (>= n or negative)?  Such a
  * forward does NOT read out of bounds -- every consumer of the table clamps the step on the device -- but its time embedding is that of the
  * last table row: *flag_out = 1 then (and stays 1 until pcdm_unet_workspace_init / pcdm_unet_prepare_timesteps clear it).  Synchronises s. */

@@ -7,8 +7,8 @@ Drop-in objects for the reference's ``pipe.unet`` / ``pipe.scheduler``
 from .parallel import run_sharded, split_list_into_chunks  # noqa: F401
 from .pipeline import (PCDMsPipeline, Simple_Stage2_InpaintDiffusionPipeline, Stage2_InpaintDiffusionPipeline,  # noqa: F401
                        Stage2_InpaintDiffusionPipelineOutput, Stage3_RefinedDiffusionPipeline)
-from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UnCLIPScheduler,  # noqa: F401
-                         UniPCMultistepScheduler)
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                         EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, UnCLIPScheduler, UniPCMultistepScheduler)
 from .unet import (Stage2_InapintUNet2DConditionModel, Stage2InpaintUNet, UNet2DConditionModel,  # noqa: F401
                    UNet2DConditionOutput)
 

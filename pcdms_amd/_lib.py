@@ -130,15 +130,19 @@ _SIGS = {
     "pcdm_attn_wide": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding": ([_P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding_rows": ([_P, _I, _P, _I, _I, _F, _P], C.c_int),
+    "pcdm_timestep_embedding_f32": ([_P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
+    "pcdm_timestep_embedding_rows_f32": ([_P, _I, _P, _I, _I, _F, _P], C.c_int),
     "pcdm_time_class_combine": ([_P, _P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_small_linear": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "pcdm_assemble_input": ([_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P], C.c_int),
+    "pcdm_assemble_input_ex": ([_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P], C.c_int),
     "pcdm_nchw_f32_to_nhwc_bf16": ([_P, _P, _I, _I, _I, _I, _P], C.c_int),
     "pcdm_nhwc_bf16_to_nchw_f32": ([_P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_f32_to_bf16": ([_P, _P, _L, _P], C.c_int),
     "pcdm_cfg_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_unipc_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_dpmpp_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_multistep_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
     "pcdm_unclip_step": ([_P, _I, _F, _P, _P, _P, C.POINTER(_F), _L, _P], C.c_int),
     "pcdm_unclip_step_dev": ([_P, _I, _F, _P, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_lincomb": ([_P, _I, C.POINTER(_P), C.POINTER(_F), _L, _P], C.c_int),
@@ -207,8 +211,10 @@ _SIGS = {
     "pcdm_unet_prepare_conditioning": ([_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P], C.c_int),
     "pcdm_unet_time_table_bytes": ([_P, _I, _I], _L),
     "pcdm_unet_prepare_timesteps": ([_P, _P, _I, _P, _P, _P], C.c_int),
+    "pcdm_unet_prepare_timesteps_f32": ([_P, _P, _I, _P, _P, _P], C.c_int),
     "pcdm_unet_set_shared_cfg_input": ([_P, _P, _I], C.c_int),
     "pcdm_unet_forward": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
+    "pcdm_unet_forward_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
     "pcdm_unet_step_overflow": ([_P, _P, C.POINTER(C.c_int), _P], C.c_int),
     "pcdm_pack_linear": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "pcdm_pack_conv3x3": ([_P, _P, _I, _I, _I, _P, _P, _P, _P], C.c_int),

@@ -7,8 +7,11 @@
 #include "image_common.h"
 
 namespace {
-// out[b, j]: diffusers Timesteps (flip_sin_to_cos => [cos | sin])
-__global__ void timestep_embedding_kernel(const int64_t* __restrict__ t_dev, const int32_t* __restrict__ step_dev,
+// out[b, j]: diffusers Timesteps (flip_sin_to_cos => [cos | sin]).  T = int64_t (the integer schedules) or float (the fractional timesteps of
+// the sigma-space samplers): the timestep is converted to fp32 once and the arithmetic is the same, so an integer-valued float gives the bits
+// of the int64 form.
+template <typename T>
+__global__ void timestep_embedding_kernel(const T* __restrict__ t_dev, const int32_t* __restrict__ step_dev,
                                           float* __restrict__ out, int B, int dim, int flip, float shift) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * dim) return;
@@ -22,7 +25,8 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t_dev, con
 }
 
 // the same for a table of timesteps: row i <- t_dev[i]
-__global__ void timestep_embedding_rows_kernel(const int64_t* __restrict__ t_dev, float* __restrict__ out, int n, int dim, int flip, float shift) {
+template <typename T>
+__global__ void timestep_embedding_rows_kernel(const T* __restrict__ t_dev, float* __restrict__ out, int n, int dim, int flip, float shift) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * dim) return;
     const int j = i % dim, half = dim / 2;
@@ -95,13 +99,29 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restri
     }
 }
 
+// the device step counter bounded into a table of `rows` rows (NULL counter: row 0), as pcdm_gemm_detail::bounded_step: a value outside
+// [0, rows) reads the nearest valid row instead of foreign memory and raises *err (every lane stores the same 1: a benign race)
+__device__ __forceinline__ int table_row(const int32_t* step_dev, int rows, int32_t* err) {
+    int st = step_dev ? *step_dev : 0;
+    if (st < 0 || st >= rows) {
+        if (err) *err = 1;
+        st = st < 0 ? 0 : rows - 1;
+    }
+    return st;
+}
+
+// scale_tab != NULL (pcdm_assemble_input_ex): the LATENT channels are multiplied in fp32 by scale_tab[row * scale_stride + scale_col]
+// (scheduler.scale_model_input) before their one rounding to bf16; NULL: pcdm_assemble_input, bit for bit
 __global__ void assemble_input_kernel(const float* __restrict__ latents, int N, int rep,
                                       const float* __restrict__ mask, int mask_b, const float* __restrict__ masked,
-                                      int masked_b, u16* __restrict__ out, int HW, int cpad) {
+                                      int masked_b, u16* __restrict__ out, int HW, int cpad, const float* __restrict__ scale_tab,
+                                      int scale_stride, int scale_col, int scale_rows, const int32_t* __restrict__ step_dev,
+                                      int32_t* __restrict__ step_error) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (b, pixel, octet)
     const int noct = cpad / 8;
     const int64_t total = (int64_t)N * rep * HW * noct;
     if (i >= total) return;
+    const float sc = scale_tab ? scale_tab[(int64_t)table_row(step_dev, scale_rows, step_error) * scale_stride + scale_col] : 1.f;
     const int oc = (int)(i % noct);
     const int64_t bp = i / noct;
     const int pix = (int)(bp % HW), b = (int)(bp / HW);
@@ -111,8 +131,10 @@ __global__ void assemble_input_kernel(const float* __restrict__ latents, int N, 
         const int c = oc * 8 + e;
         float v = 0.f;
         const int c0 = mask ? 5 : 4;   // no mask channel: [latents | masked] (the stage-3 refinement input)
-        if (c < 4) v = latents[((int64_t)(b % N) * 4 + c) * HW + pix];
-        else if (mask && c == 4) v = mask[(int64_t)(mask_b == 1 ? 0 : b) * HW + pix];
+        if (c < 4) {
+            v = latents[((int64_t)(b % N) * 4 + c) * HW + pix];
+            if (scale_tab) v = v * sc;
+        } else if (mask && c == 4) v = mask[(int64_t)(mask_b == 1 ? 0 : b) * HW + pix];
         else if (c >= c0 && c < c0 + 4) v = masked[((int64_t)(masked_b == 1 ? 0 : b) * 4 + (c - c0)) * HW + pix];
         o[e] = f2bf(v);
     }
@@ -215,6 +237,83 @@ __global__ void dpmpp_step_kernel(const float* __restrict__ eps, int cfg, float 
     if (noise_all) v += c[5] * noise_all[(int64_t)st * n + i];
     x[i] = v;
     m1[i] = m0;
+}
+
+// Euler / Euler-ancestral / LMS / PNDM (PLMS) steps as ONE elementwise kernel on five static fp32 state slots: every one of them is linear in
+// (x, a saved sample xs, eps, three older eps h1..h3, noise) with host-known scalars, row `row` of a DEVICE table (include/pcdm.h,
+// PCDM_MS_*).  Per element, with e the CFG-combined eps (fmaf(g, e_cond - e_uncond, e_uncond), as the neighbours under -ffp-contract=fast):
+//   x' = fma(c_z, z, fma(c_3, h3, fma(c_2, h2, fma(c_1, h1, fma(c_0, e, fma(c_s, xs, c_x * x))))))     (one product, then FUSED multiply-adds in
+//        this order; the z term only when a noise table is given and c_z != 0)
+//   save != 0: xs <- x (old);  push != 0: h3 <- h2, h2 <- h1, h1 <- e;  x <- x'
+// Every element is owned by one lane (no atomics).  Lanes [0, n / 4) take four consecutive elements (16-byte accesses where the address
+// allows, e.g. not on the second CFG half or a noise row of an n that is no multiple of 4), lanes [n / 4, n / 4 + n % 4) one tail element each.
+struct MsRow { float cx, cs, c0, c1, c2, c3, cz; bool save, push; };
+__device__ __forceinline__ float ms_update(const MsRow& r, float x, float xs, float e, float a1, float a2, float a3, float z, bool noisy) {
+    float v = r.cx * x;
+    v = fmaf(r.cs, xs, v);
+    v = fmaf(r.c0, e, v);
+    v = fmaf(r.c1, a1, v);
+    v = fmaf(r.c2, a2, v);
+    v = fmaf(r.c3, a3, v);
+    if (noisy) v = fmaf(r.cz, z, v);
+    return v;
+}
+__device__ __forceinline__ f32x4 ms_load4(const float* p) {
+    if (((uintptr_t)p & 15) == 0) return *(const f32x4*)p;
+    return f32x4{p[0], p[1], p[2], p[3]};
+}
+__device__ __forceinline__ void ms_store4(float* p, f32x4 v) {
+    if (((uintptr_t)p & 15) == 0) { *(f32x4*)p = v; return; }
+    p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
+}
+__global__ void multistep_step_kernel(const float* __restrict__ eps, int cfg, float g, float* __restrict__ x, float* __restrict__ xs,
+                                      float* __restrict__ h1, float* __restrict__ h2, float* __restrict__ h3,
+                                      const float* __restrict__ noise_all, const float* __restrict__ coef, int rows,
+                                      const int32_t* __restrict__ step_dev, int32_t* __restrict__ step_error, int64_t n) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nvec = n >> 2;
+    if (t >= nvec + (n & 3)) return;
+    const int st = table_row(step_dev, rows, step_error);
+    const float* c = coef + (int64_t)PCDM_MS_ROW * st;
+    const MsRow r{c[PCDM_MS_CX], c[PCDM_MS_CS], c[PCDM_MS_C0], c[PCDM_MS_C1], c[PCDM_MS_C2], c[PCDM_MS_C3], c[PCDM_MS_CZ],
+                  c[PCDM_MS_SAVE] != 0.f, c[PCDM_MS_PUSH] != 0.f};
+    const bool noisy = noise_all && r.cz != 0.f;
+    const float* z = noise_all ? noise_all + (int64_t)st * n : nullptr;
+    if (t < nvec) {
+        const int64_t i = t * 4;
+        f32x4 e = ms_load4(eps + i);
+        if (cfg) {
+            const f32x4 ec = ms_load4(eps + n + i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = fmaf(g, ec[k] - e[k], e[k]);
+        }
+        const f32x4 xv = ms_load4(x + i), sv = ms_load4(xs + i), a1 = ms_load4(h1 + i), a2 = ms_load4(h2 + i), a3 = ms_load4(h3 + i);
+        f32x4 zv = {0.f, 0.f, 0.f, 0.f};
+        if (noisy) zv = ms_load4(z + i);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = ms_update(r, xv[k], sv[k], e[k], a1[k], a2[k], a3[k], zv[k], noisy);
+        if (r.save) ms_store4(xs + i, xv);
+        if (r.push) {
+            ms_store4(h3 + i, a2);
+            ms_store4(h2 + i, a1);
+            ms_store4(h1 + i, e);
+        }
+        ms_store4(x + i, o);
+    } else {
+        const int64_t i = nvec * 4 + (t - nvec);
+        float e = eps[i];
+        if (cfg) e = fmaf(g, eps[n + i] - e, e);
+        const float xv = x[i], a1 = h1[i], a2 = h2[i];
+        const float o = ms_update(r, xv, xs[i], e, a1, a2, h3[i], noisy ? z[i] : 0.f, noisy);
+        if (r.save) xs[i] = xv;
+        if (r.push) {
+            h3[i] = a2;
+            h2[i] = a1;
+            h1[i] = e;
+        }
+        x[i] = o;
+    }
 }
 
 // UnCLIPScheduler.step on a [N, n/N] vector (stage-1 prior): guided prediction -> x0 -> clip -> posterior mean (+ noise),
@@ -402,7 +501,16 @@ extern "C" int pcdm_is_emulator(void) {
 extern "C" int pcdm_timestep_embedding(const int64_t* t_dev, const int32_t* step_dev, float* out, int B, int dim,
                                        int flip_sin_to_cos, float shift, pcdm_stream_t s) {
     if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2) return -1;
-    PCDM_LAUNCH(timestep_embedding_kernel, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, step_dev,
+    PCDM_LAUNCH(timestep_embedding_kernel<int64_t>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, step_dev,
+                out, B, dim, flip_sin_to_cos, shift);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_timestep_embedding_f32(const float* t_dev, const int32_t* step_dev, float* out, int B, int dim,
+                                           int flip_sin_to_cos, float shift, pcdm_stream_t s) {
+    if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2) return -1;
+    PCDM_LAUNCH(timestep_embedding_kernel<float>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, step_dev,
                 out, B, dim, flip_sin_to_cos, shift);
     PCDM_CHECK_LAUNCH();
     return 0;
@@ -410,7 +518,14 @@ extern "C" int pcdm_timestep_embedding(const int64_t* t_dev, const int32_t* step
 
 extern "C" int pcdm_timestep_embedding_rows(const int64_t* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s) {
     if (!t_dev || !out || n <= 0 || dim <= 0 || dim % 2) return -1;
-    PCDM_LAUNCH(timestep_embedding_rows_kernel, grid1d((int64_t)n * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, out, n, dim, flip_sin_to_cos, shift);
+    PCDM_LAUNCH(timestep_embedding_rows_kernel<int64_t>, grid1d((int64_t)n * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, out, n, dim, flip_sin_to_cos, shift);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_timestep_embedding_rows_f32(const float* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s) {
+    if (!t_dev || !out || n <= 0 || dim <= 0 || dim % 2) return -1;
+    PCDM_LAUNCH(timestep_embedding_rows_kernel<float>, grid1d((int64_t)n * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, out, n, dim, flip_sin_to_cos, shift);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -437,7 +552,20 @@ extern "C" int pcdm_assemble_input(const float* latents, int N, int rep, const f
     if (!latents || !masked || !out || N <= 0 || rep <= 0 || cpad % 8 || cpad < 16) return -1;   // mask == NULL: [latents | masked]
     const int64_t total = (int64_t)N * rep * h * w * (cpad / 8);
     PCDM_LAUNCH(assemble_input_kernel, grid1d(total, 256), dim3(256), 0, (hipStream_t)s, latents, N, rep, mask, mask_b,
-                masked, masked_b, (u16*)out, h * w, cpad);
+                masked, masked_b, (u16*)out, h * w, cpad, (const float*)nullptr, 0, 0, 1, (const int32_t*)nullptr, (int32_t*)nullptr);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_assemble_input_ex(const float* latents, int N, int rep, const float* mask, int mask_b,
+                                      const float* masked, int masked_b, void* out, int h, int w, int cpad,
+                                      const float* scale_tab, int scale_stride, int scale_col, int scale_rows,
+                                      const int32_t* step_dev, int32_t* step_error, pcdm_stream_t s) {
+    if (!latents || !masked || !out || N <= 0 || rep <= 0 || h <= 0 || w <= 0 || cpad % 8 || cpad < 16) return -1;
+    if (scale_tab && (scale_rows < 1 || scale_stride < 1 || scale_col < 0 || scale_col >= scale_stride || ((uintptr_t)step_error & 3))) return -1;
+    const int64_t total = (int64_t)N * rep * h * w * (cpad / 8);
+    PCDM_LAUNCH(assemble_input_kernel, grid1d(total, 256), dim3(256), 0, (hipStream_t)s, latents, N, rep, mask, mask_b,
+                masked, masked_b, (u16*)out, h * w, cpad, scale_tab, scale_stride, scale_col, scale_rows, step_dev, step_error);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -486,6 +614,16 @@ extern "C" int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, flo
                                const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
     if (!eps || !x || !m1 || !coef || n <= 0) return -1;
     PCDM_LAUNCH(dpmpp_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, noise_all, coef, step_dev, n);
+    PCDM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pcdm_multistep_step(const float* eps, int cfg, float g, float* x, float* xs, float* h1, float* h2, float* h3,
+                                   const float* noise_all, const float* coef, int rows, const int32_t* step_dev, int32_t* step_error,
+                                   int64_t n, pcdm_stream_t s) {
+    if (!eps || !x || !xs || !h1 || !h2 || !h3 || !coef || rows < 1 || n < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(multistep_step_kernel, grid1d((n >> 2) + (n & 3), 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, xs, h1, h2, h3, noise_all,
+                coef, rows, step_dev, step_error, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

@@ -55,7 +55,7 @@ struct pcdm_unet {
         int B = 0, h = 0, w = 0, L = 0, n0 = 0, pose_b = 0, shared = 0;
         const float* time_table = nullptr;   // [steps][B][sum Cout] fp32 (pcdm_unet_prepare_timesteps), caller-owned
         int time_steps = 0;
-        const int64_t* time_t_dev = nullptr;
+        const void* time_t_dev = nullptr;    // the int64 or float timestep table the time table was computed for
     };
     std::map<const void*, WsCond> cond_of_ws;
     bool attn_fp8 = false;   // every attention with e4m3 K / V^T / Q / P operands (pcdm_unet_set_attention_fp8; BASELINE.json configs[4])
@@ -635,7 +635,7 @@ extern "C" int64_t pcdm_unet_time_table_bytes(const pcdm_unet* u, int n, int B) 
            round_up((int64_t)n * B * D * 2, kAlign);
 }
 
-extern "C" int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, int n, void* table, void* workspace, pcdm_stream_t s) {
+static int prepare_timesteps_impl(pcdm_unet* u, const void* t_dev, bool t_f32, int n, void* table, void* workspace, pcdm_stream_t s) {
     if (!u || !t_dev || n <= 0 || !table || !workspace) return -1;
     auto it = u->cond_of_ws.find(workspace);
     if (it == u->cond_of_ws.end()) { u->err = "pcdm_unet_prepare_conditioning has not run on this workspace"; return -1; }
@@ -655,7 +655,8 @@ extern "C" int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, i
     void* emb_bf = base;
     const PW *t1 = R.pw("time_embedding.linear_1"), *t2 = R.pw("time_embedding.linear_2"), *tp = R.pw("time_emb_proj");
     if (R.rc) return R.rc;
-    R.chk(pcdm_timestep_embedding_rows(t_dev, n, t_emb, (int)C0, c.flip_sin_to_cos, c.freq_shift, s), "pcdm_timestep_embedding_rows");
+    R.chk(t_f32 ? pcdm_timestep_embedding_rows_f32((const float*)t_dev, n, t_emb, (int)C0, c.flip_sin_to_cos, c.freq_shift, s)
+                : pcdm_timestep_embedding_rows((const int64_t*)t_dev, n, t_emb, (int)C0, c.flip_sin_to_cos, c.freq_shift, s), "pcdm_timestep_embedding_rows");
     for (int r0 = 0; r0 < n; r0 += 32) {   // (pcdm_small_linear takes <= 32 rows; rows are independent)
         const int nr = n - r0 < 32 ? n - r0 : 32;
         R.chk(pcdm_small_linear(t_emb + (int64_t)r0 * C0, t1->w, t1->bias, nullptr, e1 + (int64_t)r0 * D, nr, t1->K, t1->N, 0, 1, s), "pcdm_small_linear");
@@ -688,6 +689,13 @@ extern "C" int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, i
     return 0;
 }
 
+extern "C" int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, int n, void* table, void* workspace, pcdm_stream_t s) {
+    return prepare_timesteps_impl(u, t_dev, false, n, table, workspace, s);
+}
+extern "C" int pcdm_unet_prepare_timesteps_f32(pcdm_unet* u, const float* t_dev, int n, void* table, void* workspace, pcdm_stream_t s) {
+    return prepare_timesteps_impl(u, t_dev, true, n, table, workspace, s);
+}
+
 // Has a forward on this workspace read the time table with a device step counter outside [0, n)?  (the consumers clamp it and raise this flag:
 // pcdm_gemm_params.rowvec_step_count / step_error).  Synchronous 4-byte read behind everything enqueued on s.
 extern "C" int pcdm_unet_step_overflow(pcdm_unet* u, void* workspace, int* flag_out, pcdm_stream_t s) {
@@ -709,8 +717,9 @@ extern "C" int pcdm_unet_step_overflow(pcdm_unet* u, void* workspace, int* flag_
 
 // One UNet forward (pcdms_amd/unet.py::_forward_nhwc): x_in NHWC bf16 [B, h, w, conv_in.cin]; the timestep is t_dev[step_dev ? *step_dev : 0]
 // (device memory: graph-replayable); eps_out fp32 NCHW [B, out_channels, h, w].  prepare_conditioning must have run on this workspace.
-extern "C" int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* t_dev, const int32_t* step_dev, int B, int h, int w, int L,
-                                 int pose_b, void* workspace, float* eps_out, pcdm_stream_t s) {
+// (t_f32: t_dev is a float table -- pcdm_unet_forward_f32 -- else int64)
+static int unet_forward_impl(pcdm_unet* u, const void* x_in, const void* t_dev, bool t_f32, const int32_t* step_dev, int B, int h, int w, int L,
+                             int pose_b, void* workspace, float* eps_out, pcdm_stream_t s) {
     if (!u || !x_in || !t_dev || !workspace || !eps_out || make_plan(u, B, h, w, L)) return -1;
     const pcdm_unet_config& c = u->cfg;
     Run R{u, (char*)workspace, s};
@@ -735,7 +744,9 @@ extern "C" int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* 
     const int rv_count = use_table ? cit->second.time_steps : 0;          // the step counter is bounded into the table on the device (ABI 4)
     int32_t* rv_err = use_table ? R.buf<int32_t>("step_err") : nullptr;
     if (!use_table) {
-        R.chk(pcdm_timestep_embedding(t_dev, step_dev, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s), "pcdm_timestep_embedding");
+        R.chk(t_f32 ? pcdm_timestep_embedding_f32((const float*)t_dev, step_dev, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s)
+                    : pcdm_timestep_embedding((const int64_t*)t_dev, step_dev, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s),
+              "pcdm_timestep_embedding");
         const PW *t1 = R.pw("time_embedding.linear_1"), *t2 = R.pw("time_embedding.linear_2");
         if (R.rc) return R.rc;
         R.chk(pcdm_small_linear(R.buf<float>("t_emb"), t1->w, t1->bias, nullptr, R.buf<float>("e1"), B, t1->K, t1->N, 0, 1, s), "pcdm_small_linear");
@@ -982,6 +993,15 @@ extern "C" int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* 
         R.gemm(R.buf("gn"), 0, B * HW, R.pw("conv_out"), eps_out, g);
     }
     return R.rc;
+}
+
+extern "C" int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* t_dev, const int32_t* step_dev, int B, int h, int w, int L,
+                                 int pose_b, void* workspace, float* eps_out, pcdm_stream_t s) {
+    return unet_forward_impl(u, x_in, t_dev, false, step_dev, B, h, w, L, pose_b, workspace, eps_out, s);
+}
+extern "C" int pcdm_unet_forward_f32(pcdm_unet* u, const void* x_in, const float* t_dev, const int32_t* step_dev, int B, int h, int w, int L,
+                                     int pose_b, void* workspace, float* eps_out, pcdm_stream_t s) {
+    return unet_forward_impl(u, x_in, t_dev, true, step_dev, B, h, w, L, pose_b, workspace, eps_out, s);
 }
 
 // ---- weight packing for hosts without pcdms_amd.ops.pack_* (plain host loops; the caller uploads the result) ---------------------------

@@ -742,18 +742,20 @@ def flash_attn_fp8(q: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, out: to
 # ------------------------------------------------------------------------------------ small ops
 def timestep_embedding(t_dev: torch.Tensor, step_dev: Optional[torch.Tensor], out: torch.Tensor, flip: bool = True,
                        shift: float = 0.0) -> torch.Tensor:
-    assert t_dev.dtype == torch.int64 and out.dtype == torch.float32
+    """t_dev: int64 or float32 device table (a float table keeps its fractional timesteps: ``pcdm_timestep_embedding_f32``)."""
+    assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and out.dtype == torch.float32
     B, dim = out.shape
-    _chk(_lib.lib().pcdm_timestep_embedding(_ptr(t_dev), _ptr(step_dev), _ptr(out), B, dim, int(flip), shift,
-                                            _stream(out)), "pcdm_timestep_embedding")
+    fn = _lib.lib().pcdm_timestep_embedding if t_dev.dtype == torch.int64 else _lib.lib().pcdm_timestep_embedding_f32
+    _chk(fn(_ptr(t_dev), _ptr(step_dev), _ptr(out), B, dim, int(flip), shift, _stream(out)), "pcdm_timestep_embedding")
     return out
 
 
 def timestep_embedding_rows(t_dev: torch.Tensor, out: torch.Tensor, flip: bool = True, shift: float = 0.0) -> torch.Tensor:
-    """out[i, :] = Timesteps(t_dev[i]) for a whole timestep table (fp32 [n, dim])."""
-    assert t_dev.dtype == torch.int64 and out.dtype == torch.float32 and out.shape[0] == t_dev.numel() and out.is_contiguous()
-    _chk(_lib.lib().pcdm_timestep_embedding_rows(_ptr(t_dev), t_dev.numel(), _ptr(out), out.shape[1], int(flip), shift, _stream(out)),
-         "pcdm_timestep_embedding_rows")
+    """out[i, :] = Timesteps(t_dev[i]) for a whole timestep table (fp32 [n, dim]); t_dev int64 or float32 (``pcdm_timestep_embedding_rows_f32``)."""
+    assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous()
+    assert out.dtype == torch.float32 and out.shape[0] == t_dev.numel() and out.is_contiguous()
+    fn = _lib.lib().pcdm_timestep_embedding_rows if t_dev.dtype == torch.int64 else _lib.lib().pcdm_timestep_embedding_rows_f32
+    _chk(fn(_ptr(t_dev), t_dev.numel(), _ptr(out), out.shape[1], int(flip), shift, _stream(out)), "pcdm_timestep_embedding_rows")
     return out
 
 
@@ -787,6 +789,30 @@ def assemble_input(latents: torch.Tensor, rep: int, mask: Optional[torch.Tensor]
     cpad = out.shape[-1]
     _chk(_lib.lib().pcdm_assemble_input(_ptr(latents), N, rep, _ptr(mask), 1 if mask is None else mask.shape[0], _ptr(masked),
                                         masked.shape[0], _ptr(out), h, w, cpad, _stream(out)), "pcdm_assemble_input")
+    return out
+
+
+def assemble_input_ex(latents: torch.Tensor, rep: int, mask: Optional[torch.Tensor], masked: torch.Tensor, out: torch.Tensor,
+                      scale_tab: Optional[torch.Tensor] = None, scale_col: int = 0, step_dev: Optional[torch.Tensor] = None,
+                      step_error: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``assemble_input`` with ``scheduler.scale_model_input`` folded in (pcdm_assemble_input_ex): the latent channels are multiplied by
+    ``scale_tab[*step_dev, scale_col]`` (fp32 device table [rows, stride]) before their rounding to bf16; ``scale_tab=None``: ``assemble_input``."""
+    N, _, h, w = latents.shape
+    _c(latents, torch.float32); _c(masked, torch.float32); _c(out, BF16)
+    if mask is not None:
+        _c(mask, torch.float32)
+    rows = stride = 1
+    if scale_tab is not None:
+        _c(scale_tab, torch.float32)
+        assert scale_tab.dim() == 2 and 0 <= scale_col < scale_tab.shape[1]
+        rows, stride = scale_tab.shape
+    if step_dev is not None:
+        assert step_dev.dtype == torch.int32
+    if step_error is not None:
+        assert step_error.dtype == torch.int32
+    _chk(_lib.lib().pcdm_assemble_input_ex(_ptr(latents), N, rep, _ptr(mask), 1 if mask is None else mask.shape[0], _ptr(masked),
+                                           masked.shape[0], _ptr(out), h, w, out.shape[-1], _ptr(scale_tab), stride, int(scale_col), rows,
+                                           _ptr(step_dev), _ptr(step_error), _stream(out)), "pcdm_assemble_input_ex")
     return out
 
 
@@ -848,6 +874,31 @@ def dpmpp_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torc
         assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
     _chk(_lib.lib().pcdm_dpmpp_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(noise_all), _ptr(coef),
                                     _ptr(step_dev), n, _stream(x)), "pcdm_dpmpp_step")
+
+
+#: row layout of the ``pcdm_multistep_step`` table (include/pcdm.h PCDM_MS_*)
+MS_ROW, MS_CX, MS_CS, MS_C0, MS_C1, MS_C2, MS_C3, MS_CZ, MS_IN_SCALE, MS_SAVE, MS_PUSH = 12, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+
+
+def multistep_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, xs: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor,
+                   h3: torch.Tensor, noise_all: Optional[torch.Tensor], coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None,
+                   step_error: Optional[torch.Tensor] = None) -> None:
+    """pcdm_multistep_step: CFG combine + one Euler / Euler-ancestral / LMS / PLMS step in place on (x, xs, h1, h2, h3); coef fp32
+    [rows, 12], noise_all fp32 [rows, x.numel()] (or None), both on the device."""
+    n = x.numel()
+    for t in (eps, x, xs, h1, h2, h3, coef):
+        _c(t, torch.float32)
+    assert eps.numel() == (2 * n if cfg else n) and xs.numel() == h1.numel() == h2.numel() == h3.numel() == n
+    assert coef.dim() == 2 and coef.shape[1] == MS_ROW
+    assert len({t.data_ptr() for t in (x, xs, h1, h2, h3)}) == 5, "the five state slots are distinct buffers"
+    if noise_all is not None:
+        assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
+    if step_dev is not None:
+        assert step_dev.dtype == torch.int32
+    if step_error is not None:
+        assert step_error.dtype == torch.int32
+    _chk(_lib.lib().pcdm_multistep_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(xs), _ptr(h1), _ptr(h2), _ptr(h3), _ptr(noise_all),
+                                        _ptr(coef), coef.shape[0], _ptr(step_dev), _ptr(step_error), n, _stream(x)), "pcdm_multistep_step")
 
 
 def unclip_step(pred: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, noise: Optional[torch.Tensor], out: torch.Tensor,

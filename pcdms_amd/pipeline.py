@@ -6,13 +6,16 @@ conditioning assembly (:430-466), same loop body (:496-519).  Two execution mode
 kernels:
 
 * ``mode="reference"`` -- literally the reference's loop: ``cat`` inputs, ``self.unet(...)``,
-  CFG combine, ``self.scheduler.step(...)`` with any scheduler object (UniPC / DDIM / DDPM / DPM-Solver++).
-* ``mode="fused"`` (default for DDIM with eta = 0, for UniPC, the shipped driver's scheduler, and for DPM-Solver++ in both its
-  ODE ("DPM++ 2M") and SDE forms: all are per-step LINEAR updates with host-known coefficients; the SDE form's noise is drawn
-  up front into a per-step table) -- per step: ``pcdm_assemble_input`` -> UNet schedule -> ``pcdm_cfg_step`` /
-  ``pcdm_unipc_step`` / ``pcdm_dpmpp_step`` (CFG + scheduler update from a device-side coefficient table; multistep history
-  lives in static slots) -> ``pcdm_advance_step``; the step is captured once in a hipGraph and replayed ``num_inference_steps`` times (the step
-  index lives in device memory), which removes ~700 host launches per step from the critical path.
+  CFG combine, ``self.scheduler.step(...)`` with any scheduler object (UniPC / DDIM / DDPM / DPM-Solver++ /
+  Euler / Euler-ancestral / LMS / PNDM).
+* ``mode="fused"`` (default for DDIM with eta = 0, for UniPC, the shipped driver's scheduler, for DPM-Solver++ in both its
+  ODE ("DPM++ 2M") and SDE forms, and for Euler, Euler-ancestral, LMS and PNDM: all are per-step LINEAR updates with host-known
+  coefficients; the noise of the stochastic ones is drawn up front into a per-step table) -- per step: ``pcdm_assemble_input``
+  (``pcdm_assemble_input_ex`` with the step's ``scale_model_input`` factor for the sigma-space samplers) -> UNet schedule ->
+  ``pcdm_cfg_step`` / ``pcdm_unipc_step`` / ``pcdm_dpmpp_step`` / ``pcdm_multistep_step`` (CFG + scheduler update from a device-side
+  coefficient table; multistep history lives in static slots) -> ``pcdm_advance_step``; the step is captured once in a hipGraph and
+  replayed ``len(scheduler.timesteps)`` times (PNDM: ``num_inference_steps + 1``; the step index lives in device memory), which
+  removes ~700 host launches per step from the critical path.
 
 VAE encode/decode are outside the hot path: pass ``masked_latents``
 (= vae.encode(vae_image).sample * scaling_factor, ref :443-444) and read ``output.latents``.
@@ -26,7 +29,8 @@ from typing import Any, Callable, List, Optional, Union
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, _step_noise
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, _step_noise,
+                         _TableStepScheduler)
 from .unet import Stage2_InapintUNet2DConditionModel
 
 
@@ -88,8 +92,9 @@ class Stage2_InpaintDiffusionPipeline:
         """``Stage2_InpaintDiffusionPipeline.from_pretrained(sd21_dir, torch_dtype=...)`` as the drivers call it
         (/root/reference/stage2_batchtest_inpaint_model.py:123): loads ``vae/`` and ``unet/`` (stock SD UNet; the driver then
         assigns its own ``pipe.unet`` / ``pipe.scheduler``, :125-132) and builds a scheduler from
-        ``scheduler/scheduler_config.json``.  SD-2.1 ships a PNDM config; PNDM is not part of this path, so any scheduler
-        class that is not implemented here becomes a ``DDIMScheduler`` with the shared keys (the drivers replace it anyway).
+        ``scheduler/scheduler_config.json``, by class name.  SD-2.1 ships a PNDM config (``skip_prk_steps=True``): the pipeline
+        then holds a ``PNDMScheduler``, as the reference's does.  A class name that ``pcdms_amd.schedulers`` does not have
+        still becomes a ``DDIMScheduler`` with the shared keys.
         Text encoder / tokenizer / safety checker of the directory are not used by the stage-2 call and are not loaded."""
         import json
         from pathlib import Path
@@ -228,9 +233,11 @@ class Stage2_InpaintDiffusionPipeline:
         linear = linear or (isinstance(self.scheduler, UniPCMultistepScheduler) and self.scheduler.config.solver_order <= 2)
         # DPM-Solver++ (ODE and SDE form): linear in (x, eps, m1, noise); the SDE noise comes from a per-call table of the same draws
         linear = linear or isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        # Euler / Euler-ancestral / LMS / PNDM: linear in (x, a saved sample, eps and its history, noise) on five static slots
+        linear = linear or isinstance(self.scheduler, _TableStepScheduler)
         mode = mode or ("fused" if linear else "reference")
         if mode == "fused" and not linear:
-            raise ValueError("mode='fused' needs a scheduler with one linear update per step (DDIM with eta=0, UniPC, DPM-Solver++)")
+            raise ValueError("mode='fused' needs a scheduler with one linear update per step (DDIM with eta=0, UniPC, DPM-Solver++, Euler, Euler-ancestral, LMS, PNDM)")
 
         if mode == "reference":
             # the literal loop: bare unet(...) calls.  The UNet recognises the step-invariant tensors by identity (it keeps
@@ -282,7 +289,11 @@ class Stage2_InpaintDiffusionPipeline:
     def _step_eager(self, st):
         unet = self.unet
         B, h, w = st["B"], st["h"], st["w"]
-        x_in = ops.assemble_input(st["lat"], st["rep"], st["mask"], st["masked"], st["x_in"])
+        if st.get("scaled"):   # scale_model_input: the latent channels times this step's 1 / sqrt(sigma^2 + 1), read from the step table
+            x_in = ops.assemble_input_ex(st["lat"], st["rep"], st["mask"], st["masked"], st["x_in"], st["coef"], ops.MS_IN_SCALE, st["step"],
+                                         st["step_err"])
+        else:
+            x_in = ops.assemble_input(st["lat"], st["rep"], st["mask"], st["masked"], st["x_in"])
         if st.get("ctx") is not None:
             eps = st["ctx"].forward(x_in, st["timesteps"], st["step"], B, h, w, st["pose_b"], out=st["eps_c"])
         else:
@@ -297,6 +308,8 @@ class Stage2_InpaintDiffusionPipeline:
             ops.unipc_step(e, cfg, g, st["lat"], st["m1"], st["m2"], st["last"], st["coef"], st["step"])
         elif st["dpm"]:
             ops.dpmpp_step(e, cfg, g, st["lat"], st["m1"], st["noise"], st["coef"], st["step"])
+        elif st.get("ms"):
+            ops.multistep_step(e, cfg, g, st["lat"], st["xs"], st["h1"], st["h2"], st["h3"], st["noise"], st["coef"], st["step"], st["step_err"])
         else:
             ops.cfg_step(e, cfg, g, st["lat"], st["lat"], st["coef"], st["step"])
         ops.advance_step(st["step"])
@@ -308,6 +321,9 @@ class Stage2_InpaintDiffusionPipeline:
                 st[k].zero_()
         elif st.get("dpm"):
             st["m1"].zero_()
+        elif st.get("ms"):
+            for k in ("xs", "h1", "h2", "h3"):
+                st[k].zero_()
 
     def _run_fused(self, lat, mask, masked, pose_cond, feature_f, prior_embed, timesteps, do_cfg, g, eta, use_graph,
                    callback, callback_steps, guidance_rescale=0.0, zero_uncond=False, shared_halves=False, generator=None):
@@ -321,23 +337,30 @@ class Stage2_InpaintDiffusionPipeline:
         n0 = N if (do_cfg and zero_uncond) else 0
         unipc = isinstance(self.scheduler, UniPCMultistepScheduler)
         dpm = isinstance(self.scheduler, DPMSolverMultistepScheduler)
-        sde = dpm and self.scheduler.stochastic
-        kind = "unipc" if unipc else ("dpm_sde" if sde else "dpm") if dpm else "linear"
+        ms = isinstance(self.scheduler, _TableStepScheduler)     # Euler / Euler-ancestral / LMS / PNDM: pcdm_multistep_step
+        sde = (dpm or ms) and self.scheduler.stochastic
+        scaled = ms and self.scheduler.scales_input
+        kind = "unipc" if unipc else ("dpm_sde" if sde else "dpm") if dpm else ("ms", sde, scaled) if ms else "linear"
+        tdt = torch.float32 if timesteps.dtype.is_floating_point else torch.int64   # the scheduler's own: float32 tables keep fractional timesteps
         key = (B, h, w, n, rep, n0, tuple(feature_f.shape), None if mask is None else tuple(mask.shape), tuple(masked.shape),
-               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, kind, bool(shared_halves))
+               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, kind, bool(shared_halves), tdt)
         st = self._st if self._graph_key == key else {}
         if not st:
-            st.update(B=B, h=h, w=w, rep=rep, unipc=unipc, dpm=dpm, noise=None,
+            st.update(B=B, h=h, w=w, rep=rep, unipc=unipc, dpm=dpm, ms=ms, scaled=scaled, noise=None,
                       lat=torch.empty_like(lat), mask=None if mask is None else torch.empty_like(mask), masked=torch.empty_like(masked),
                       eps_g=torch.empty_like(lat),
                       x_in=torch.empty(B, h, w, 64, dtype=ops.BF16, device=dev),
                       step=torch.zeros(1, dtype=torch.int32, device=dev),
-                      timesteps=torch.empty(n, dtype=torch.int64, device=dev),
-                      coef=torch.empty(n, 12 if unipc else 8 if dpm else 4, dtype=torch.float32, device=dev))
+                      timesteps=torch.empty(n, dtype=tdt, device=dev),
+                      coef=torch.empty(n, 12 if (unipc or ms) else 8 if dpm else 4, dtype=torch.float32, device=dev))
             if unipc:   # UniPC history (two stored x0-predictions, last corrected sample): static slots, zeroed per call
                 st.update(m1=torch.zeros_like(lat), m2=torch.zeros_like(lat), last=torch.zeros_like(lat))
             if dpm:     # DPM-Solver++ history (the previous x0-prediction) and, for the SDE form, the per-step noise table [n, numel]
                 st.update(m1=torch.zeros_like(lat), noise=torch.empty(n, lat.numel(), dtype=torch.float32, device=dev) if sde else None)
+            if ms:      # saved sample + three eps-history slots, zeroed per call; the flag the table readers raise for a counter outside the table
+                st.update(xs=torch.zeros_like(lat), h1=torch.zeros_like(lat), h2=torch.zeros_like(lat), h3=torch.zeros_like(lat),
+                          step_err=torch.zeros(1, dtype=torch.int32, device=dev),
+                          noise=torch.empty(n, lat.numel(), dtype=torch.float32, device=dev) if sde else None)
             self._graph = None
         # Per call: the static input slots the captured step reads are refilled, and the step-invariant conditioning (class
         # embedding, NHWC pose, the 16 cross-attention K / V^T) is recomputed EAGERLY into the UNet's shape-keyed buffers --
@@ -348,11 +371,13 @@ class Stage2_InpaintDiffusionPipeline:
         if mask is not None:
             st["mask"].copy_(mask)
         st["masked"].copy_(masked)
-        st["timesteps"].copy_(timesteps.to(dev))
+        st["timesteps"].copy_(timesteps.to(dev, tdt))
+        if ms:
+            st["step_err"].zero_()
         # (with the timestep table: the time / class embedding MLPs and every time_emb_proj for ALL steps, once per call)
         st["cond"] = unet.prepare_conditioning(B, h, w, feature_f, prior_embed, pose_cond, zero_ctx_batches=n0, shared_cfg_input=shared_halves,
                                                timesteps=st["timesteps"])
-        st["coef"].copy_(self.scheduler.coefficient_table(device=dev) if (unipc or dpm) else self.scheduler.coefficient_table(eta, device=dev))
+        st["coef"].copy_(self.scheduler.coefficient_table(device=dev) if (unipc or dpm or ms) else self.scheduler.coefficient_table(eta, device=dev))
         if sde:   # the draws the literal loop would make, one per step in step order, refilled per call outside the captured step
             for i in range(n):
                 st["noise"][i].copy_(_step_noise(lat.shape, generator, dev).reshape(-1))
@@ -431,7 +456,7 @@ class Stage2_InpaintDiffusionPipeline:
         out = st["lat"].clone()
         # the device step counter indexes the per-call time table inside the kernels: they bound it (a counter beyond the table is clamped,
         # never an out-of-bounds read) and raise a flag -- read once per sampling call (one 4-byte copy behind the loop)
-        if hasattr(unet, "step_overflow") and unet.step_overflow():
+        if (hasattr(unet, "step_overflow") and unet.step_overflow()) or (ms and int(st["step_err"].item()) != 0):
             raise RuntimeError("the device step counter left the time-embedding table of this sampling call (clamped on the device): "
                                "the schedule ran more steps than prepare_conditioning(timesteps=...) was given")
         return out

@@ -4,15 +4,17 @@ The reference uses three diffusers 0.24.0 schedulers at this boundary (SURVEY.md
 ``UniPCMultistepScheduler`` (stage2_batchtest_inpaint_model.py:132), ``DDIMScheduler``
 (pcdms_kaggle_demo.ipynb cell 15 -- the configuration BASELINE.json's metric names) and
 ``DDPMScheduler`` (stage2_train_inpaint_model.py:175,361).  The pipelines type the slot as any
-``KarrasDiffusionSchedulers`` member; of those, ``DPMSolverMultistepScheduler`` ("DPM++ 2M", with or without
-Karras sigmas, and its SDE form) is here too.  Call sites:
+``KarrasDiffusionSchedulers`` member; the six that ``Simple_Stage2_InpaintDiffusionPipeline.__init__`` names
+(src/pipelines/stage2_inpaint_pipeline.py:547-558) are all here: DDIM, ``DPMSolverMultistepScheduler`` ("DPM++ 2M", with or without
+Karras sigmas, and its SDE form), ``PNDMScheduler`` (PLMS, the SD-2.1 directory's own scheduler), ``LMSDiscreteScheduler``,
+``EulerDiscreteScheduler`` and ``EulerAncestralDiscreteScheduler``.  Call sites:
 src/pipelines/stage2_inpaint_pipeline.py:472-473 (set_timesteps / timesteps), :386
 (init_noise_sigma), :494 (order), :500 (scale_model_input), :519 (step; ``eta`` / ``generator`` are
 passed only if ``inspect.signature(step)`` has them, :313-321).
 
 Coefficient math is scalar host code (float64, tables in fp32 where diffusers keeps them in fp32);
 every tensor update is a hand-written HIP kernel from libpcdm.so (``pcdm_lincomb`` /
-``pcdm_cfg_step`` / ``pcdm_dpmpp_step``).  Tensors must be on the GPU: there is no CPU tensor path.
+``pcdm_cfg_step`` / ``pcdm_dpmpp_step`` / ``pcdm_multistep_step``).  Tensors must be on the GPU: there is no CPU tensor path.
 """
 from __future__ import annotations
 
@@ -604,6 +606,317 @@ class DPMSolverMultistepScheduler(_Base):
         self._step_index += 1
         prev = prev.to(sample.dtype)
         return (prev,) if not return_dict else SchedulerOutput(prev)
+
+
+class _TableStepScheduler(_Base):
+    """Shared machinery of the four samplers that run on ``pcdm_multistep_step`` (include/pcdm.h): each is, at every step of a fresh run, a
+    linear map on (x, a saved sample xs, eps, three older eps h1..h3, noise) whose scalars depend on the step index and the step count only.
+    ``_rows()`` holds them (float64 [len(timesteps), 12]); ``coefficient_table`` is the fused pipeline's device table, ``step`` runs the same
+    kernel on one row with the history in slots this object owns.  The step index is a counter that ``set_timesteps`` resets.  Stateful: one
+    instance per in-flight sampling run."""
+
+    #: does ``scale_model_input`` change the sample (the row's ``in_scale`` is then not 1)?
+    scales_input = False
+    stochastic = False
+
+    def _reset_state(self):
+        self._step_index: Optional[int] = None
+        self._slots: Optional[List[torch.Tensor]] = None     # [xs, h1, h2, h3]
+        self._table: Optional[torch.Tensor] = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def _rows(self) -> np.ndarray:
+        raise NotImplementedError
+
+    def coefficient_table(self, device=None) -> torch.Tensor:
+        """fp32 [len(timesteps), 12] rows {c_x, c_s, c_0, c_1, c_2, c_3, c_z, in_scale, save, push, 0, 0} for ``pcdm_multistep_step`` and
+        ``pcdm_assemble_input_ex`` (include/pcdm.h): the rows ``step`` uses at each step of a fresh run; float64 host math, stored as fp32."""
+        return torch.from_numpy(self._rows().astype(np.float32)).to(device)
+
+    def _init_step_index(self, timestep) -> int:
+        return 0
+
+    def _index(self, timestep) -> int:
+        if self._step_index is None:
+            self._step_index = self._init_step_index(timestep)
+        return self._step_index
+
+    def _run_step(self, model_output: torch.Tensor, sample: torch.Tensor, timestep, noise: Optional[torch.Tensor], return_dict: bool):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        i = self._index(timestep)
+        if i >= len(self.timesteps):
+            raise IndexError(f"step {i} of a schedule of {len(self.timesteps)} steps: call set_timesteps before another run")
+        e, x = _f32(model_output), _f32(sample)
+        if self._table is None or self._table.device != x.device:
+            self._table = self.coefficient_table(device=x.device)
+        if self._slots is None or self._slots[0].shape != x.shape or self._slots[0].device != x.device:
+            self._slots = [torch.zeros_like(x) for _ in range(4)]
+        prev = x.clone()
+        z = None if noise is None else _f32(noise.to(x.device)).reshape(1, -1)
+        ops.multistep_step(e, False, 1.0, prev, *self._slots, z, self._table[i:i + 1])
+        self._step_index = i + 1
+        prev = prev.to(sample.dtype)
+        return (prev,) if not return_dict else SchedulerOutput(prev)
+
+
+class _SigmaScheduler(_TableStepScheduler):
+    """The sigma-space ("k-diffusion") schedule shared by Euler, Euler-ancestral and LMS in diffusers 0.24.0: float32 timesteps (fractional
+    with ``timestep_spacing="linspace"``), ``sigma = sqrt((1 - ac) / ac)`` interpolated at them (fp32, as diffusers keeps the table) with a
+    final 0, the sample held at scale ``sigma`` (``init_noise_sigma``) and divided by ``sqrt(sigma^2 + 1)`` in front of the UNet."""
+
+    scales_input = True
+    _has_karras = False
+
+    def _check(self, name: str):
+        c = self.config
+        why = None
+        if c.prediction_type != "epsilon":
+            why = f"prediction_type {c.prediction_type!r} (epsilon only)"
+        elif c.timestep_spacing not in ("linspace", "leading", "trailing"):
+            why = f"timestep_spacing {c.timestep_spacing!r}"
+        elif c.get("interpolation_type", "linear") != "linear" and name == "EulerDiscreteScheduler":
+            why = f"interpolation_type {c.interpolation_type!r} (linear only)"
+        elif c.get("timestep_type", "discrete") != "discrete" and name == "EulerDiscreteScheduler":
+            why = f"timestep_type {c.timestep_type!r} (discrete only)"
+        elif c.get("rescale_betas_zero_snr", False):
+            why = "rescale_betas_zero_snr"
+        if why is not None:
+            raise NotImplementedError(f"{name}: {why} is not implemented")
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        c, T, n = self.config, self.config.num_train_timesteps, num_inference_steps
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
+        else:   # trailing
+            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
+        sig = _train_sigmas(self.alphas_cumprod)
+        sigmas = np.interp(ts, np.arange(0, len(sig)), sig)
+        if self._has_karras and c.get("use_karras_sigmas", False):   # timesteps of the Karras sigmas stay fractional (not rounded)
+            sigmas = _convert_to_karras(sigmas, n)
+            ts = _sigma_to_t(sigmas, np.log(sig)).astype(np.float32)
+        self.sigmas = np.concatenate([sigmas, [0.0]]).astype(np.float32)
+        self.num_inference_steps = n
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts_list = [float(v) for v in ts]
+        self._reset_state()
+
+    @property
+    def init_noise_sigma(self) -> float:
+        smax = float(np.max(self.sigmas))
+        return smax if self.config.timestep_spacing in ("linspace", "trailing") else math.sqrt(smax * smax + 1.0)
+
+    def _in_scale(self, i: int) -> float:
+        s = float(self.sigmas[i])
+        return 1.0 / math.sqrt(s * s + 1.0)
+
+    def _init_step_index(self, timestep) -> int:
+        if timestep is None:
+            return 0
+        t = float(timestep)
+        idx = [k for k, v in enumerate(self._ts_list) if v == t]
+        if not idx:
+            raise ValueError(f"timestep {t} is not in this schedule")
+        return idx[1] if len(idx) > 1 else idx[0]     # (as diffusers: a repeated timestep means the second occurrence when a run starts there)
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        """sample / sqrt(sigma_i^2 + 1) at the current step (one ``pcdm_lincomb`` launch; the fused pipeline folds the same fp32 scalar
+        into ``pcdm_assemble_input_ex``)."""
+        i = self._index(timestep)
+        x = _f32(sample)
+        return ops.lincomb(torch.empty_like(x), [x], [self._in_scale(i)]).to(sample.dtype)
+
+    def _blank_rows(self) -> np.ndarray:
+        n = len(self._ts_list)
+        rows = np.zeros((n, ops.MS_ROW), dtype=np.float64)
+        rows[:, ops.MS_CX] = 1.0
+        rows[:, ops.MS_IN_SCALE] = [self._in_scale(i) for i in range(n)]
+        return rows
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.24.0 ``EulerDiscreteScheduler`` restated (that source could not be read here: parity is against the float64 restatement
+    in tests/test_karras_samplers.py, upstream parity is unpinned; tools/compare_with_diffusers.py checks it where diffusers is installed).
+    Epsilon prediction, ``interpolation_type="linear"``, with or without Karras sigmas, ``timestep_spacing`` linspace / leading / trailing;
+    the step is the deterministic one, ``s_churn = 0``:  x' = x + (sigma_{i+1} - sigma_i) eps."""
+
+    _has_karras = True
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, timestep_spacing="linspace",
+                     steps_offset=0)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self._check("EulerDiscreteScheduler")
+        self.set_timesteps(self.config.num_train_timesteps)
+
+    def _rows(self) -> np.ndarray:
+        rows = self._blank_rows()
+        s = self.sigmas.astype(np.float64)
+        rows[:, ops.MS_C0] = s[1:] - s[:-1]
+        return rows
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, s_churn: float = 0.0, s_tmin: float = 0.0,
+             s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True):
+        if s_churn != 0.0:
+            raise NotImplementedError("EulerDiscreteScheduler.step: s_churn != 0 (stochastic churn) is not implemented")
+        return self._run_step(model_output, sample, timestep, None, return_dict)
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.24.0 ``EulerAncestralDiscreteScheduler`` restated (parity as for ``EulerDiscreteScheduler``), epsilon prediction:
+    sigma_up = sqrt(sigma_to^2 (sigma_from^2 - sigma_to^2) / sigma_from^2), sigma_down = sqrt(sigma_to^2 - sigma_up^2),
+    x' = x + (sigma_down - sigma_from) eps + sigma_up z.  z is ``_step_noise``: one draw per step in step order (the last step draws too,
+    with weight 0), which the fused pipeline makes up front into its per-step table."""
+
+    stochastic = True
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self._check("EulerAncestralDiscreteScheduler")
+        self.set_timesteps(self.config.num_train_timesteps)
+
+    def _rows(self) -> np.ndarray:
+        rows = self._blank_rows()
+        s = self.sigmas.astype(np.float64)
+        s_from, s_to = s[:-1], s[1:]
+        up = np.sqrt(s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2)
+        down = np.sqrt(s_to ** 2 - up ** 2)
+        rows[:, ops.MS_C0] = down - s_from
+        rows[:, ops.MS_CZ] = up
+        return rows
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        if variance_noise is None:
+            variance_noise = _step_noise(sample.shape, generator, sample.device)
+        return self._run_step(model_output, sample, timestep, variance_noise, return_dict)
+
+
+def _lms_coefficients(sigmas: np.ndarray, i: int, order: int) -> List[float]:
+    """c_k, k < order: the integral from sigma_i to sigma_{i+1} of the Lagrange basis polynomial of node sigma_{i-k} over the nodes
+    sigma_i .. sigma_{i-order+1}.  Closed form in float64: the polynomial is expanded in u = tau - sigma_i (small numbers near the
+    interval), integrated term by term and evaluated at u = sigma_{i+1} - sigma_i."""
+    s = np.asarray(sigmas, dtype=np.float64)
+    d = s[i + 1] - s[i]
+    out = []
+    for k in range(order):
+        roots = [s[i - j] - s[i] for j in range(order) if j != k]
+        den = float(np.prod([s[i - k] - s[i - j] for j in range(order) if j != k])) if roots else 1.0
+        poly = np.poly(roots) if roots else np.array([1.0])      # highest power first
+        out.append(float(np.polyval(np.polyint(poly), d)) / den)
+    return out
+
+
+class LMSDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.24.0 ``LMSDiscreteScheduler`` restated (parity as for ``EulerDiscreteScheduler``), epsilon prediction, order 4:
+    x' = x + sum_k c_k eps_{i-k} over the last min(i + 1, 4) model outputs, c_k the integral of the Lagrange basis polynomial over
+    [sigma_i, sigma_{i+1}].  diffusers integrates with adaptive quadrature (scipy, 1e-4 relative); here the polynomial is integrated in
+    CLOSED FORM in float64 (``_lms_coefficients``), which is the exact value that quadrature approximates.  scipy is not a dependency."""
+
+    _has_karras = True
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     use_karras_sigmas=False, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0)
+    lms_order = 4
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self._check("LMSDiscreteScheduler")
+        self.set_timesteps(self.config.num_train_timesteps)
+
+    def _rows(self) -> np.ndarray:
+        rows = self._blank_rows()
+        for i in range(rows.shape[0]):
+            order = min(i + 1, self.lms_order)
+            rows[i, ops.MS_C0:ops.MS_C0 + order] = _lms_coefficients(self.sigmas, i, order)
+        rows[:, ops.MS_PUSH] = 1.0
+        return rows
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, order: int = 4, return_dict: bool = True):
+        if order != self.lms_order:
+            raise NotImplementedError("LMSDiscreteScheduler.step: order 4 only")
+        return self._run_step(model_output, sample, timestep, None, return_dict)
+
+
+class PNDMScheduler(_TableStepScheduler):
+    """diffusers 0.24.0 ``PNDMScheduler`` restated (parity as for ``EulerDiscreteScheduler``) in its ``skip_prk_steps=True`` form, the
+    PLMS sampler of the SD-2.1 ``scheduler_config.json``; epsilon prediction.  The Runge-Kutta warm-up is not built: ``skip_prk_steps``
+    defaults to True HERE (diffusers: False) and an explicit False is refused.
+
+    ``timesteps`` repeats the second entry, so n steps are n + 1 UNet calls.  Call 0 steps with eps and saves the sample; call 1 redoes
+    that step from the SAVED sample with (eps + e_1) / 2 and pushes no history; from then on the 2-, 3- and 4-term Adams-Bashforth weights.
+    x' = sqrt(a_p / a_t) x - (a_p - a_t) e' / (a_t sqrt(1 - a_p) + sqrt(a_t (1 - a_t) a_p))."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     skip_prk_steps=True, set_alpha_to_one=False, prediction_type="epsilon", timestep_spacing="leading", steps_offset=0)
+    _AB = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        why = None
+        if not c.skip_prk_steps:
+            why = "skip_prk_steps=False (the Runge-Kutta warm-up steps)"
+        elif c.prediction_type != "epsilon":
+            why = f"prediction_type {c.prediction_type!r} (epsilon only)"
+        elif c.timestep_spacing not in ("linspace", "leading", "trailing"):
+            why = f"timestep_spacing {c.timestep_spacing!r}"
+        if why is not None:
+            raise NotImplementedError(f"PNDMScheduler: {why} is not implemented")
+        self.final_alpha_cumprod = 1.0 if c.set_alpha_to_one else float(self._ac[0])
+        self._reset_state()
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        c, T, n = self.config, self.config.num_train_timesteps, num_inference_steps
+        if n > T:
+            raise ValueError("`num_inference_steps` cannot be larger than `num_train_timesteps`")
+        if c.timestep_spacing == "leading":
+            t = (np.arange(0, n) * (T // n)).round() + c.steps_offset
+        elif c.timestep_spacing == "linspace":
+            t = np.linspace(0, T - 1, n).round()
+        else:   # trailing
+            t = np.round(np.arange(T, 0, -T / n))[::-1] - 1
+        t = t.astype(np.int64)
+        ts = np.concatenate([t[:-1], t[-2:-1], t[-1:]])[::-1].copy()
+        self.num_inference_steps = n
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts_list = [int(v) for v in ts]
+        self._reset_state()
+
+    def _transfer(self, t: int, tp: int) -> Tuple[float, float]:
+        """(c_x, c_e) of ``_get_prev_sample``: x' = c_x x + c_e e'."""
+        a_t = float(self._ac[t])
+        a_p = float(self._ac[tp]) if tp >= 0 else self.final_alpha_cumprod
+        den = a_t * math.sqrt(1 - a_p) + math.sqrt(a_t * (1 - a_t) * a_p)
+        return math.sqrt(a_p / a_t), -(a_p - a_t) / den
+
+    def _rows(self) -> np.ndarray:
+        m = len(self._ts_list)
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        rows = np.zeros((m, ops.MS_ROW), dtype=np.float64)
+        rows[:, ops.MS_IN_SCALE] = 1.0
+        for k, t in enumerate(self._ts_list):
+            if k == 1:       # the repeated timestep: from the saved sample, over the same interval as call 0, with the averaged eps
+                cx, ce = self._transfer(t + ratio, t)
+                rows[k, ops.MS_CS], rows[k, ops.MS_C0], rows[k, ops.MS_C1] = cx, 0.5 * ce, 0.5 * ce
+                continue
+            cx, ce = self._transfer(t, t - ratio)
+            w = self._AB[1 if k == 0 else min(k, 4)]
+            rows[k, ops.MS_CX] = cx
+            rows[k, ops.MS_C0:ops.MS_C0 + len(w)] = [ce * v for v in w]
+            rows[k, ops.MS_PUSH] = 1.0
+            rows[k, ops.MS_SAVE] = 1.0 if k == 0 else 0.0
+        return rows
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
+        return self._run_step(model_output, sample, timestep, None, return_dict)
 
 
 class UnCLIPScheduler(_Base):

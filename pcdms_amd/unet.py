@@ -327,7 +327,7 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         ``conv_in``, the first GroupNorm and the contraction of the first ``conv1``: that prefix is then computed for B/2 entries and
         written for both halves (``pcdm_gemm_params.dup_rows``) -- the same arithmetic, executed once.
 
-        ``timesteps`` (device int64 table of the whole schedule): the time / class embedding MLPs and all 22 ``time_emb_proj`` rows depend
+        ``timesteps`` (device int64 or float32 table of the whole schedule): the time / class embedding MLPs and all 22 ``time_emb_proj`` rows depend
         on the timestep and the class labels only, so they are computed HERE for every step (one GEMM with M = steps x B rows) instead of
         five launches per denoise step; a forward that is given the table's device step counter (``_forward_nhwc(..., step_dev)``) picks
         its block through ``pcdm_gemm_params.rowvec_step``.  Same per-row arithmetic as the per-step launches (bit-identical)."""
@@ -407,8 +407,9 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         boc = self._boc
         temb_dim = boc[0] * 4
         ts = timesteps.reshape(-1)
-        if ts.dtype != torch.int64 or ts.device != dev:
-            ts = ts.to(dev, torch.int64)
+        tdt = torch.float32 if ts.dtype.is_floating_point else torch.int64   # a float table keeps its fractional timesteps
+        if ts.dtype != tdt or ts.device != dev or not ts.is_contiguous():
+            ts = ts.to(dev, tdt).contiguous()
         n = ts.numel()
         t_emb = ops.timestep_embedding_rows(ts, self._buf("tt_emb", (n, boc[0]), torch.float32), cfg.flip_sin_to_cos, float(cfg.freq_shift))
         e1 = self._buf("tt_e1", (n, temb_dim), torch.float32)
@@ -539,8 +540,11 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         # ---- 1. time / class embedding (ref :661-708)
         if torch.is_tensor(timestep):
             t_dev = timestep.reshape(-1)[:1] if step_dev is None else timestep.reshape(-1)
-            if t_dev.dtype != torch.int64 or t_dev.device != dev:
-                t_dev = t_dev.to(dev, torch.int64)
+            tdt = torch.float32 if t_dev.dtype.is_floating_point else torch.int64   # float timesteps are not truncated (749.25 stays 749.25)
+            if t_dev.dtype != tdt or t_dev.device != dev or not t_dev.is_contiguous():
+                t_dev = t_dev.to(dev, tdt).contiguous()
+        elif isinstance(timestep, float):
+            t_dev = torch.tensor([timestep], dtype=torch.float32, device=dev)
         else:
             t_dev = torch.tensor([int(timestep)], dtype=torch.int64, device=dev)
         cls_emb, pose_nhwc, kv, L, nzero = cond.cls_emb, cond.pose_nhwc, cond.kv, cond.L, cond.n0

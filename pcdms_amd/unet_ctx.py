@@ -158,16 +158,16 @@ class UNetContext:
     def prepare_timesteps(self, t_dev: torch.Tensor, B: int, h: int, w: int) -> None:
         """After ``prepare_conditioning``: the time / class embeddings and every ``time_emb_proj`` for ALL steps of the device timestep table
         ``t_dev`` (``pcdm_unet_prepare_timesteps``); ``forward`` calls that pass the same ``t_dev`` with a step counter then launch nothing for them."""
-        assert t_dev.dtype == torch.int64 and t_dev.is_contiguous() and t_dev.device == self.unet.device
+        assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and t_dev.device == self.unet.device
         n = t_dev.numel()
+        fn = _lib.lib().pcdm_unet_prepare_timesteps if t_dev.dtype == torch.int64 else _lib.lib().pcdm_unet_prepare_timesteps_f32
         nbytes = _lib.lib().pcdm_unet_time_table_bytes(self._h, n, B)
         key = ("ttab", n, B)
         tab = self._ws.get(key)
         if tab is None:
             tab = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.unet.device)
         ws = self.workspace(B, h, w, self._L)
-        self._chk(_lib.lib().pcdm_unet_prepare_timesteps(self._h, t_dev.data_ptr(), n, tab.data_ptr(), ws.data_ptr(), ops._stream(ws)),
-                  "pcdm_unet_prepare_timesteps")
+        self._chk(fn(self._h, t_dev.data_ptr(), n, tab.data_ptr(), ws.data_ptr(), ops._stream(ws)), "pcdm_unet_prepare_timesteps")
 
     def step_overflow(self, B: int, h: int, w: int) -> bool:
         """``pcdm_unet_step_overflow``: did a forward on this shape's workspace find the device step counter outside the prepared time table?
@@ -181,13 +181,14 @@ class UNetContext:
     @torch.no_grad()
     def forward(self, x_in: torch.Tensor, t_dev: torch.Tensor, step_dev: Optional[torch.Tensor], B: int, h: int, w: int, pose_b: int,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_in NHWC bf16 [B, h, w, conv_in.cin]; t_dev int64 device tensor; returns fp32 NCHW eps."""
-        assert x_in.dtype == ops.BF16 and x_in.is_contiguous() and t_dev.dtype == torch.int64
+        """x_in NHWC bf16 [B, h, w, conv_in.cin]; t_dev int64 or float32 device tensor; returns fp32 NCHW eps."""
+        assert x_in.dtype == ops.BF16 and x_in.is_contiguous() and t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous()
+        fn = _lib.lib().pcdm_unet_forward if t_dev.dtype == torch.int64 else _lib.lib().pcdm_unet_forward_f32
         if self._pack_gen != self.unet._pack_gen:
             raise RuntimeError("the UNet's weights were re-packed: build a new UNetContext")
         ws = self.workspace(B, h, w, self._L)
         if out is None:
             out = torch.empty(B, self.unet.config.out_channels, h, w, dtype=torch.float32, device=x_in.device)
-        self._chk(_lib.lib().pcdm_unet_forward(self._h, x_in.data_ptr(), t_dev.data_ptr(), None if step_dev is None else step_dev.data_ptr(),
-                                               B, h, w, self._L, pose_b, ws.data_ptr(), out.data_ptr(), ops._stream(x_in)), "pcdm_unet_forward")
+        self._chk(fn(self._h, x_in.data_ptr(), t_dev.data_ptr(), None if step_dev is None else step_dev.data_ptr(),
+                     B, h, w, self._L, pose_b, ws.data_ptr(), out.data_ptr(), ops._stream(x_in)), "pcdm_unet_forward")
         return out

@@ -90,14 +90,22 @@ def main():
               P.DPMSolverMultistepScheduler(**sd21_sched, use_karras_sigmas=True), 20),
              ("dpmpp_2m_sde", diffusers.DPMSolverMultistepScheduler(**sd21_sched, algorithm_type="sde-dpmsolver++"),
               P.DPMSolverMultistepScheduler(**sd21_sched, algorithm_type="sde-dpmsolver++"), 20),
+             ("euler", diffusers.EulerDiscreteScheduler(**sd21_sched), P.EulerDiscreteScheduler(**sd21_sched), 20),
+             ("euler_karras", diffusers.EulerDiscreteScheduler(**sd21_sched, use_karras_sigmas=True),
+              P.EulerDiscreteScheduler(**sd21_sched, use_karras_sigmas=True), 20),
+             ("euler_a", diffusers.EulerAncestralDiscreteScheduler(**sd21_sched), P.EulerAncestralDiscreteScheduler(**sd21_sched), 20),
+             ("lms", diffusers.LMSDiscreteScheduler(**sd21_sched), P.LMSDiscreteScheduler(**sd21_sched), 20),
+             ("pndm", diffusers.PNDMScheduler(**sd21_sched, skip_prk_steps=True, set_alpha_to_one=False, steps_offset=1),
+              P.PNDMScheduler(**sd21_sched, skip_prk_steps=True, set_alpha_to_one=False, steps_offset=1), 20),
              ("unclip", diffusers.UnCLIPScheduler(**P.UnCLIPScheduler.KANDINSKY22_PRIOR), P.UnCLIPScheduler(**P.UnCLIPScheduler.KANDINSKY22_PRIOR), 20)]
     for name, theirs, ours, n in pairs:
         theirs.set_timesteps(n)
         ours.set_timesteps(n)
-        assert [int(t) for t in theirs.timesteps] == [int(t) for t in ours.timesteps], name
+        assert torch.allclose(theirs.timesteps.double().cpu(), ours.timesteps.double().cpu(), rtol=1e-6, atol=1e-3), name   # (float: Euler / LMS)
+        float_ts = ours.timesteps.dtype.is_floating_point
         xs_t = xs_o = torch.randn(2, 4, 8, 8, generator=g)
         worst = 0.0
-        ts = [int(t) for t in theirs.timesteps]
+        ts = [float(t) if float_ts else int(t) for t in theirs.timesteps]
         for i, t in enumerate(ts):
             eps = torch.randn(2, 4, 8, 8, generator=g)
             noise = torch.randn(2, 4, 8, 8, generator=g)
@@ -108,7 +116,7 @@ def main():
                 torch.manual_seed(1234 + i)
                 nt = theirs.step(eps, t, xs_t, prev_timestep=prev).prev_sample
                 no = ours.step(eps.to(dev), t, xs_o.to(dev), prev_timestep=prev, variance_noise=noise.to(dev)).prev_sample
-            elif name == "dpmpp_2m_sde":   # both draw the step's noise from the generator passed: give each the same seed
+            elif name in ("dpmpp_2m_sde", "euler_a"):   # both draw the step's noise from the generator passed: give each the same seed
                 nt = theirs.step(eps, t, xs_t, generator=torch.Generator().manual_seed(1234 + i)).prev_sample
                 no = ours.step(eps.to(dev), t, xs_o.to(dev), generator=torch.Generator().manual_seed(1234 + i)).prev_sample
             else:
@@ -116,7 +124,7 @@ def main():
                 no = ours.step(eps.to(dev), t, xs_o.to(dev)).prev_sample
             worst = max(worst, rel(no, nt))
             xs_t, xs_o = nt, nt   # re-synchronise every step: per-step comparison
-        report[f"scheduler_{name}"] = (worst, 2e-5)
+        report[f"scheduler_{name}"] = (worst, 2e-3 if name == "lms" else 2e-5)   # (diffusers' LMS quadrature stops at 1e-4 relative)
 
     # ---- 3. VAE ---------------------------------------------------------------------------------------------------
     vcfg = dict(block_out_channels=(64, 64, 128, 128) if a.tiny else (128, 256, 512, 512), layers_per_block=2, latent_channels=4,

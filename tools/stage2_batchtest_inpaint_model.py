@@ -151,9 +151,13 @@ def inference(args, rank, select_test_datas):
         low_cpu_mem_usage=False, ignore_mismatched_sizes=True).to(device)
     pipe.unet.load_state_dict(unet_dict)
     scheduler = getattr(args, "scheduler", "unipc")
+    simple = {"ddim": P.DDIMScheduler, "euler": P.EulerDiscreteScheduler, "euler_a": P.EulerAncestralDiscreteScheduler,
+              "lms": P.LMSDiscreteScheduler, "pndm": P.PNDMScheduler}
     if scheduler == "unipc":   # the reference driver's choice
         pipe.scheduler = P.UniPCMultistepScheduler.from_config(pipe.scheduler.config)
-    else:                      # DPM++ 2M, its Karras-sigma and SDE forms
+    elif scheduler in simple:  # the other members of the reference's scheduler slot (src/pipelines/stage2_inpaint_pipeline.py:547-558)
+        pipe.scheduler = simple[scheduler].from_config(pipe.scheduler.config)
+    else:                      # DPM++ 2M ("dpmpp"), its Karras-sigma and SDE forms
         pipe.scheduler = P.DPMSolverMultistepScheduler.from_config(
             pipe.scheduler.config, use_karras_sigmas=scheduler == "dpmpp_2m_karras",
             algorithm_type="sde-dpmsolver++" if scheduler == "dpmpp_2m_sde" else "dpmsolver++")
@@ -292,7 +296,8 @@ def build_parser():
     p.add_argument("--pose_det_widen_factor", type=float, default=1.0, help="widen_factor of --pose_det_weights (YOLOX-l: 1)")
     p.add_argument("--pose_det_deepen_factor", type=float, default=1.0, help="deepen_factor of --pose_det_weights (YOLOX-l: 1)")
     p.add_argument("--pose_det_num_classes", type=int, default=80, help="classes of --pose_det_weights (COCO: 80; class 0 is the person)")
-    p.add_argument("--scheduler", choices=("unipc", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde"), default="unipc")
+    p.add_argument("--scheduler", choices=("unipc", "ddim", "dpmpp", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde", "euler", "euler_a", "lms", "pndm"),
+                   default="unipc")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p
 

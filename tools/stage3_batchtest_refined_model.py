@@ -58,7 +58,10 @@ def inference(args, rank, select_test_datas):
     pipe.unet = P.UNet2DConditionModel.from_pretrained(args.pretrained_model_name_or_path, subfolder="unet", in_channels=8,
                                                        low_cpu_mem_usage=False, ignore_mismatched_sizes=True).to(device)
     pipe.unet.load_state_dict(unet_dict)
-    pipe.scheduler = P.UniPCMultistepScheduler.from_config(pipe.scheduler.config)
+    sched_cls = {"unipc": P.UniPCMultistepScheduler, "ddim": P.DDIMScheduler, "dpmpp": P.DPMSolverMultistepScheduler,
+                 "euler": P.EulerDiscreteScheduler, "euler_a": P.EulerAncestralDiscreteScheduler, "lms": P.LMSDiscreteScheduler,
+                 "pndm": P.PNDMScheduler}[getattr(args, "scheduler", "unipc")]   # (unipc: the reference driver's choice)
+    pipe.scheduler = sched_cls.from_config(pipe.scheduler.config)
     pipe.enable_xformers_memory_efficient_attention()
     print("====================== json_data: {}, model load finish ===================".format(args.json_path.split("/")[-1]))
     W, H = args.img_width, args.img_height
@@ -130,6 +133,8 @@ def build_parser():
     p.add_argument("--guidance_scale", type=_guidance, default=2.0)   # ref: type=int, default=2.0 => "2.0" by default, "2" when given
     p.add_argument("--seed_number", type=int, default=42)
     p.add_argument("--num_inference_steps", type=int, default=20)
+    p.add_argument("--scheduler", choices=("unipc", "ddim", "dpmpp", "euler", "euler_a", "lms", "pndm"), default="unipc",
+                   help="the sampler in the pipeline's scheduler slot (unipc: the reference driver's)")
     p.add_argument("--img_width", type=int, default=512)
     p.add_argument("--img_height", type=int, default=512)
     p.add_argument("--calculate_metrics", action="store_true")
