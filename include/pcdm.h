@@ -373,6 +373,21 @@ int pcdm_advance_step(int32_t* step_dev, pcdm_stream_t s);
 /* out NHWC bf16 [B, 2H, 2W, C] <- in [B * H * W, 4 * C] bf16 (columns = phase 2a + b major, then channel): out[b, 2y + a, 2x + bb, c] =
  * in[(b, y, x), (2a + bb) C + c].  The second half of the phase-decomposed Upsample2D convolution (pcdm_gemm_params.tap_lut).  C % 8 == 0. */
 int pcdm_pixel_shuffle2(const void* in, void* out, int B, int H, int W, int C, pcdm_stream_t s);
+/* FreeU (arXiv 2309.11497; diffusers 0.24.0 apply_freeu / fourier_filter, threshold 1) in front of one decoder resnet's [hidden | skip] concat.
+ * hidden bf16 [B * H * W, C1], skip bf16 [B * H * W, C2] (NHWC rows):
+ *   hidden_out[:, c] = bf16(float(hidden[:, c]) * b) for c < C1 / 2, = hidden[:, c] above (hidden_out == hidden: in place, the upper half is not touched);
+ *   skip_out = ifftn(ifftshift(fftshift(fftn(skip)) * mask)).real over (H, W) with mask = 1 except s on [H/2 - 1 : H/2 + 1, W/2 - 1 : W/2 + 1],
+ *   evaluated as skip + (s - 1) * (the projection onto the frequencies ky in {0, -1}, kx in {0, -1}, one frequency along an axis of length 1):
+ *   plane sums (fixed order) and correction in fp64 -- fp32 sums miss one ulp where the correction cancels an element --, rounded to bf16 once:
+ *   every element within one bf16 ulp of the fp64 FFT form; s = 1 returns skip bit for bit.  skip is not written (skip_out == skip is
+ *   refused).  Reruns are bit-identical, a plane's result does not depend on B, nothing is allocated: graph-capturable.
+ * One launch while H * W <= 355 (the (image, 64-channel) slab stays in LDS); larger planes take two launches through `workspace`
+ * (pcdm_freeu_ws_bytes bytes, 16-byte aligned, no initialisation; 0 bytes -- workspace may be NULL -- for the one-launch sizes).
+ * Any H, W >= 1.  C1 and C2 must be multiples of 8: anything else, a NULL or not 16-byte aligned tensor, B, H or W < 1, B > 65535 or
+ * H * W > 2^24 returns -1 without launching (pcdm_freeu_ws_bytes: -1). */
+int64_t pcdm_freeu_ws_bytes(int B, int H, int W, int C1, int C2);
+int pcdm_freeu(const void* hidden, void* hidden_out, const void* skip, void* skip_out, int B, int H, int W, int C1, int C2, float b, float s,
+               void* workspace, pcdm_stream_t st);
 
 /* ---- Image metrics of the evaluation drivers (stage2_batchtest_inpaint_model.py:203-219, stage3_batchtest_refined_model.py): score the N decoded
  * samples of a pair against the target on the device and keep the best one, without a host round trip.
@@ -835,6 +850,11 @@ int pcdm_unet_set_tile(pcdm_unet* u, int ln, int M, int Npad, int K, int conv, i
 /* 1: every attention of the UNet with OCP e4m3 K / V^T / Q / P operands (pcdm_quantize_fp8 + pcdm_flash_attn_fp8; BASELINE.json configs[4]), 0
  * (default): bf16.  Switch before pcdm_unet_prepare_conditioning (it quantises the context K / V^T) and before capturing a graph. */
 int pcdm_unet_set_attention_fp8(pcdm_unet* u, int on);
+/* FreeU in the two lowest-resolution up blocks (pcdm_freeu in front of every resnet of up block 0 with (b1, s1) and of up block 1 with (b2, s2);
+ * diffusers 0.24.0 enable_freeu(s1, s2, b1, b2)); on = 0 (default): off, the four floats are ignored.  Only while it is on does the plan hold
+ * the FreeU buffers ("fu_s", "fu_ws"): with it off pcdm_unet_workspace_bytes / _layout answer as without this call.  Switching re-plans (buffers
+ * move: run pcdm_unet_workspace_init and pcdm_unet_prepare_conditioning again, and capture again); changing only the floats does not. */
+int pcdm_unet_set_freeu(pcdm_unet* u, int on, float s1, float s2, float b1, float b2);
 int pcdm_unet_get_tile(const pcdm_unet* u, int ln, int M, int Npad, int K, int conv, int stride, int upsample, int epilogue, int two_source, int residual,
                        int flag, int* tile, int* split_k);
 int64_t pcdm_unet_workspace_bytes(pcdm_unet* u, int B, int h, int w, int L);

@@ -152,6 +152,8 @@ _SIGS = {
     "pcdm_image_to_uint8": ([_P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_advance_step": ([_P, _P], C.c_int),
     "pcdm_pixel_shuffle2": ([_P, _P, _I, _I, _I, _I, _P], C.c_int),
+    "pcdm_freeu_ws_bytes": ([_I, _I, _I, _I, _I], _L),
+    "pcdm_freeu": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P], C.c_int),
     "pcdm_metrics_ws_bytes": ([_I, _I, _I, _I, _F], _L),
     "pcdm_ssim": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _F, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_psnr": ([_P, _I, _I, _I, _W4, _P, _I, _I, _I, _W4, _I, _I, _F, _P, _P, _P, _L, _P], C.c_int),
@@ -205,6 +207,7 @@ _SIGS = {
     "pcdm_unet_set_vector": ([_P, C.c_char_p, _P, _I], C.c_int),
     "pcdm_unet_set_tile": ([_P] + [_I] * 13, C.c_int),
     "pcdm_unet_set_attention_fp8": ([_P, _I], C.c_int),
+    "pcdm_unet_set_freeu": ([_P, _I, _F, _F, _F, _F], C.c_int),
     "pcdm_unet_get_tile": ([_P] + [_I] * 11 + [C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
     "pcdm_unet_workspace_bytes": ([_P, _I, _I, _I, _I], _L),
     "pcdm_unet_workspace_init": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),

@@ -44,7 +44,7 @@ struct pcdm_unet {
     std::map<std::string, Vec> v;
     std::map<TileKey, std::pair<int, int>> tiles;
     // plan (valid for plan_key)
-    std::tuple<int, int, int, int, int64_t> plan_key{0, 0, 0, 0, 0};   // B, h, w, L, the red-zone size it was laid out with
+    std::tuple<int, int, int, int, int64_t, int> plan_key{0, 0, 0, 0, 0, 0};   // B, h, w, L, the red-zone size it was laid out with, FreeU on
     std::map<std::string, Buf> bufs;
     std::vector<std::string> order;   // the names of bufs in offset order (pcdm_unet_workspace_layout)
     int64_t ws_bytes = 0;
@@ -59,6 +59,8 @@ struct pcdm_unet {
     };
     std::map<const void*, WsCond> cond_of_ws;
     bool attn_fp8 = false;   // every attention with e4m3 K / V^T / Q / P operands (pcdm_unet_set_attention_fp8; BASELINE.json configs[4])
+    bool freeu = false;      // pcdm_freeu in front of every resnet of up blocks 0 and 1 (pcdm_unet_set_freeu): {s1, s2}, {b1, b2}
+    float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f};
     std::string err;
 };
 
@@ -351,7 +353,7 @@ std::vector<std::tuple<std::string, int, int>> transformers(const pcdm_unet_conf
 }
 
 int make_plan(pcdm_unet* u, int B, int h, int w, int L) {
-    const auto key = std::make_tuple(B, h, w, L, g_redzone);
+    const auto key = std::make_tuple(B, h, w, L, g_redzone, (int)u->freeu);
     if (u->plan_key == key && !u->bufs.empty()) return 0;
     const pcdm_unet_config& c = u->cfg;
     u->bufs.clear();
@@ -430,6 +432,19 @@ int make_plan(pcdm_unet* u, int B, int h, int w, int L) {
                 P.add("ds" + std::to_string(i), (int64_t)B * hh * ww * c.block_out_channels[i] * 2);
             }
         }
+    }
+    if (u->freeu) {   // FreeU (pcdm_unet_set_freeu): the filtered skip of the resnet in flight and, for planes beyond the one-launch size, the coefficients
+        int64_t fs = 0, fw = 0;
+        std::vector<std::pair<int, int>> hw{{h, w}};
+        for (int i = 1; i < n; ++i) hw.emplace_back((hw.back().first - 1) / 2 + 1, (hw.back().second - 1) / 2 + 1);
+        for (int i = 0; i < n && i < 2; ++i) {
+            const int lv = n - 1 - i, out = c.block_out_channels[lv], inc = c.block_out_channels[lv > 0 ? lv - 1 : 0];
+            const int cs = std::max(out, inc), hh = hw[lv].first, ww = hw[lv].second;
+            fs = std::max(fs, (int64_t)B * hh * ww * cs * 2);
+            fw = std::max(fw, pcdm_freeu_ws_bytes(B, hh, ww, 8, cs));
+        }
+        P.add("fu_s", fs);
+        if (fw > 0) P.add("fu_ws", fw);
     }
     {   // the live regions in offset order (a name laid out twice keeps its last region only: Planner::add)
         std::vector<std::string> live;
@@ -511,6 +526,17 @@ extern "C" int pcdm_unet_set_attention_fp8(pcdm_unet* u, int on) {
     if (!u) return -1;
     if ((on != 0) != u->attn_fp8) u->cond_of_ws.clear();   // (outstanding conditionings lack / carry the e4m3 copies)
     u->attn_fp8 = on != 0;
+    return 0;
+}
+
+extern "C" int pcdm_unet_set_freeu(pcdm_unet* u, int on, float s1, float s2, float b1, float b2) {
+    if (!u) return -1;
+    if ((on != 0) != u->freeu) {   // (the plan gains / loses the FreeU buffers: every buffer moves)
+        u->bufs.clear();
+        u->cond_of_ws.clear();
+    }
+    u->freeu = on != 0;
+    u->fu_s[0] = s1; u->fu_s[1] = s2; u->fu_b[0] = b1; u->fu_b[1] = b2;
     return 0;
 }
 
@@ -947,17 +973,25 @@ static int unet_forward_impl(pcdm_unet* u, const void* x_in, const void* t_dev, 
     const int cm = c.block_out_channels[n - 1];
     x = resnet("mid_block.resnets.0.", x, cm, nullptr, 0, hh * ww, hh, ww, "r", true);
     x = transformer("mid_block.attentions.0.", x, cm, c.heads[n - 1], hh * ww, "r2");
-    x = resnet("mid_block.resnets.1.", x, cm, nullptr, 0, hh * ww, hh, ww, "r", true);
+    x = resnet("mid_block.resnets.1.", x, cm, nullptr, 0, hh * ww, hh, ww, "r", !u->freeu);   // (FreeU reads the bf16 tensor: no deferred reduce)
     // ---- 5. up (ref :789-814)
     int cx = cm;
     for (int i = 0; i < n && !R.rc; ++i) {
         const int co = c.block_out_channels[n - 1 - i];
+        const bool fu = u->freeu && i < 2;   // FreeU: the backbone scaled in place (nothing else reads it), the filtered skip in "fu_s"
         for (int j = 0; j < Lb + 1; ++j) {
-            const Skip sk = skips.back();
+            Skip sk = skips.back();
             skips.pop_back();
             if (sk.hh != hh || sk.ww != ww) { u->err = "skip size mismatch"; return -1; }
+            if (fu && !R.rc) {
+                void* fs = R.buf("fu_s");
+                R.chk(pcdm_freeu(x, const_cast<void*>(x), sk.p, fs, B, hh, ww, cx, sk.ch, u->fu_b[i], u->fu_s[i],
+                                 u->bufs.count("fu_ws") ? R.buf("fu_ws") : nullptr, s), "pcdm_freeu");
+                sk.p = fs;
+            }
+            // (a resnet whose output the next resnet's FreeU reads materialises it: no reduce deferred to a GroupNorm)
             x = resnet("up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", x, cx, sk.p, sk.ch, hh * ww, hh, ww, (j + i) % 2 ? "r" : "rb",
-                       has_cross(c, n - 1 - i) || j < Lb || i == n - 1);
+                       has_cross(c, n - 1 - i) || (j < Lb ? !fu : i == n - 1));
             cx = co;
             if (has_cross(c, n - 1 - i))
                 x = transformer("up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", x, co, c.heads[n - 1 - i], hh * ww, j % 2 ? "u" : "ub");
@@ -979,7 +1013,7 @@ static int unet_forward_impl(pcdm_unet* u, const void* x_in, const void* t_dev, 
             }
             Run::G g;
             g.conv = 1; g.B = B; g.Hi = hh; g.Wi = ww; g.Ho = ho; g.Wo = wo; g.upsample = 1;
-            g.defer = 1;   // -> the next block's norm1
+            g.defer = (u->freeu && i + 1 < 2) ? 0 : 1;   // -> the next block's norm1 (or its FreeU, which reads the bf16 tensor)
             R.gemm(x, 0, B * ho * wo, R.pw("up_blocks." + std::to_string(i) + ".upsamplers.0.conv"), R.buf("us"), g);
             x = R.buf("us");
             hh = ho; ww = wo;

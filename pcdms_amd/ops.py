@@ -283,6 +283,26 @@ def pixel_shuffle2(x: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, C
     return out
 
 
+def freeu_ws_bytes(B: int, H: int, W: int, C1: int, C2: int) -> int:
+    """Workspace bytes of ``freeu`` at this shape: 0 while the plane takes the one-launch form; -1 for a shape ``pcdm_freeu`` refuses."""
+    return int(_lib.lib().pcdm_freeu_ws_bytes(B, H, W, C1, C2))
+
+
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, skip_out: torch.Tensor, B: int, H: int, W: int, b: float, s: float,
+          hidden_out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """FreeU in front of one decoder resnet (``pcdm_freeu``): ``hidden`` [B*H*W, C1] and ``skip`` [B*H*W, C2] bf16 NHWC rows; the first C1/2 backbone
+    channels times ``b`` (in place unless ``hidden_out`` is given), the skip's lowest frequencies times ``s`` into ``skip_out`` (``skip`` itself is
+    not written).  ``ws``: ``freeu_ws_bytes`` bytes for planes beyond the one-launch size.  Returns ``(hidden_out, skip_out)``."""
+    ho = hidden if hidden_out is None else hidden_out
+    assert all(t.dtype == BF16 and t.is_contiguous() and t.dim() == 2 and t.shape[0] == B * H * W for t in (hidden, ho, skip, skip_out))
+    assert ho.shape == hidden.shape and skip_out.shape == skip.shape
+    C1, C2 = hidden.shape[1], skip.shape[1]
+    call = lambda: _lib.lib().pcdm_freeu(_ptr(hidden), _ptr(ho), _ptr(skip), _ptr(skip_out), B, H, W, C1, C2, float(b), float(s), _ptr(ws),  # noqa: E731
+                                         _stream(skip))
+    _chk(_launch(skip, call, "freeu", 14.0 * B * H * W * C2, (B, H, W, C1, C2)), "pcdm_freeu")
+    return ho, skip_out
+
+
 def pack_geglu(w: torch.Tensor, bias: torch.Tensor, device) -> PackedWeight:
     """GEGLU proj weight [2*D, K] (rows [h | gate]) -> rows interleaved per 64 as [32 h | 32 gate]."""
     w = w.float()

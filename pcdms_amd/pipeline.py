@@ -129,6 +129,17 @@ class Stage2_InpaintDiffusionPipeline:
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         self.unet.set_use_memory_efficient_attention_xformers(True, attention_op)
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """``pipe.enable_freeu(s1, s2, b1, b2)`` of the reference's pipelines (src/pipelines/PCDMs_pipeline.py:744-762): forwarded to ``self.unet``.
+        The state is part of what a captured step depends on: changing it re-captures (``_run_fused``)."""
+        if not hasattr(self.unet, "enable_freeu"):
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """ref src/pipelines/PCDMs_pipeline.py:765-768."""
+        self.unet.disable_freeu()
+
     def prepare_extra_step_kwargs(self, generator, eta):
         """ref :307-322."""
         params = set(inspect.signature(self.scheduler.step).parameters.keys())
@@ -385,6 +396,10 @@ class Stage2_InpaintDiffusionPipeline:
         if st.get("gr", guidance_rescale) != guidance_rescale:
             self._graph = None
         st["gr"] = guidance_rescale
+        freeu = getattr(unet, "_freeu", None)   # on / off and the four floats: another launch list, other kernel arguments
+        if st.get("freeu", freeu) != freeu:
+            self._graph = None
+        st["freeu"] = freeu
         # pipe.unet replaced, weights re-packed (load_state_dict / .to), or a split-K workspace re-allocated: re-capture
         w_gen = (id(unet), getattr(unet, "_pack_gen", 0), ops.workspace_generation(dev))
         if st.get("w_gen") != w_gen:

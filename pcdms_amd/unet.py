@@ -160,6 +160,7 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         self._cache: Dict[str, Any] = {}
         self._cond_gen = 0   # bumped by every prepare_conditioning (the shared K/V, pose and class-embedding buffers are rewritten)
         self._attn_fp8 = False   # e4m3 K / V^T / Q / P attention on the MX-scaled fp8 MFMA (set_attention_precision)
+        self._freeu: Optional[Tuple[float, float, float, float]] = None   # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def set_use_memory_efficient_attention_xformers(self, valid: bool = True, attention_op=None):
@@ -179,6 +180,25 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             self._pack_gen = getattr(self, "_pack_gen", 0) + 1   # (pipelines re-capture their hipGraph)
             self._cache.clear()
             self._cond_gen += 1                                   # outstanding Conditioning objects lack / carry the e4m3 K, V^T
+        return self
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (arXiv 2309.11497) as diffusers 0.24.0 ``UNet2DConditionModel.enable_freeu(s1, s2, b1, b2)`` defines it: in up block 0 (``b1``,
+        ``s1``) and up block 1 (``b2``, ``s2``), in front of every resnet's ``[hidden | skip]`` concat, the first half of the backbone channels is
+        scaled by ``b`` and the 2 x 2 lowest frequencies of the skip by ``s`` (``ops.freeu``: one launch per affected resnet).  Offered on both UNet
+        classes (the reference's own stage-2 class builds its up blocks without a ``resolution_idx``, so there the call only works on the stock
+        stage-3 model).  Changing the state invalidates captured graphs and ``UNetContext`` objects (the pipelines rebuild both)."""
+        state = tuple(float(v) for v in (s1, s2, b1, b2))
+        if state != self._freeu:
+            self._freeu = state
+            self._pack_gen = getattr(self, "_pack_gen", 0) + 1
+        return self
+
+    def disable_freeu(self):
+        """Back to the plain decoder: the launches, buffers and bits of a model on which FreeU was never enabled."""
+        if self._freeu is not None:
+            self._freeu = None
+            self._pack_gen = getattr(self, "_pack_gen", 0) + 1
         return self
 
     def _invalidate(self):
@@ -721,17 +741,28 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
         # ---- 4. mid (ref :775-783)
         x = resnet("mid_block.resnets.0.", x, None, hh * ww, hh, ww, "r", gn_next=True)
         x = transformer("mid_block.attentions.0.", x, hh * ww, "r2")
-        x = resnet("mid_block.resnets.1.", x, None, hh * ww, hh, ww, "r", gn_next=True)
+        # FreeU (enable_freeu): in front of every resnet of up blocks 0 and 1 one launch scales the backbone in place (nothing else reads it) and
+        # writes the filtered skip to "fu_s" (the skip buffers stay as they are: the taps read them after the forward).  Its producers -- the
+        # previous resnet, the transformer, the upsampler -- materialise their bf16 tensor: no split-K reduce is deferred to a GroupNorm there.
+        fu = self._freeu
+        x = resnet("mid_block.resnets.1.", x, None, hh * ww, hh, ww, "r", gn_next=fu is None)
         # ---- 5. up (ref :789-814)
         rev = list(reversed(boc))
         for i, typ in enumerate(cfg.up_block_types):
+            fu_i = fu is not None and i < 2
             for j in range(L_ + 1):
                 sk, sh, sw = skips.pop()
                 assert (sh, sw) == (hh, ww)
                 cross = typ == "CrossAttnUpBlock2D"
-                # next consumer: the transformer's norm, the next resnet's norm1, conv_norm_out -- or the upsampling conv (no norm)
+                if fu_i:
+                    nb = ops.freeu_ws_bytes(B, hh, ww, x.shape[1], sk.shape[1])
+                    x, sk = ops.freeu(x, sk, self._buf("fu_s", tuple(sk.shape)), B, hh, ww, fu[2 + i], fu[i],
+                                      ws=self._buf("fu_ws", (nb,), torch.uint8) if nb > 0 else None)
+                    if taps is not None:
+                        tap(f"up_blocks.{i}.resnets.{j}.fu_h", x), tap(f"up_blocks.{i}.resnets.{j}.fu_s", sk)
+                # next consumer: the transformer's norm, the next resnet's norm1, conv_norm_out -- or the upsampling conv (no norm), or FreeU
                 x = resnet(f"up_blocks.{i}.resnets.{j}.", x, sk, hh * ww, hh, ww, "r" if (j + i) % 2 else "rb",
-                           gn_next=cross or j < L_ or i == nlev - 1)
+                           gn_next=cross or (not fu_i if j < L_ else i == nlev - 1))
                 if cross:
                     x = transformer(f"up_blocks.{i}.attentions.{j}.", x, hh * ww, "u" if j % 2 else "ub")
                     if taps is not None:
@@ -749,7 +780,8 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
                     continue
                 x = ops.gemm(x.view(B, hh, ww, rev[i]), W[f"up_blocks.{i}.upsamplers.0.conv."],
                              self._buf("us", (B * ho * wo, rev[i])),
-                             conv=dict(B=B, Hi=hh, Wi=ww, Ho=ho, Wo=wo, upsample=1), defer_reduce=True)    # -> the next block's norm1
+                             conv=dict(B=B, Hi=hh, Wi=ww, Ho=ho, Wo=wo, upsample=1),
+                             defer_reduce=None if (fu is not None and i + 1 < 2) else True)    # -> the next block's norm1 (or its FreeU)
                 if taps is not None:
                     tap(f"up_blocks.{i}.upsamplers.0.out", x)
                 hh, ww = ho, wo

@@ -41,6 +41,9 @@ class UNetContext:
             raise RuntimeError("pcdm_unet_create rejected the topology")
         self._attn_fp8 = bool(unet._attn_fp8)
         self._chk(lib.pcdm_unet_set_attention_fp8(self._h, int(self._attn_fp8)), "pcdm_unet_set_attention_fp8")
+        self._freeu = unet._freeu   # (s1, s2, b1, b2) or None; a later enable_freeu / disable_freeu bumps unet._pack_gen: build a new context
+        if self._freeu is not None:
+            self._chk(lib.pcdm_unet_set_freeu(self._h, 1, *self._freeu), "pcdm_unet_set_freeu")
         self._keep = []       # tensors the context points into
         self._ws = {}
         self._register()

@@ -150,6 +150,8 @@ def inference(args, rank, select_test_datas):
         projection_class_embeddings_input_dim=unet_dict["class_embedding.linear_1.weight"].shape[1], torch_dtype=torch.float16,
         low_cpu_mem_usage=False, ignore_mismatched_sizes=True).to(device)
     pipe.unet.load_state_dict(unet_dict)
+    if getattr(args, "freeu", None):   # opt-in (no reference counterpart in this driver): pipe.enable_freeu(s1, s2, b1, b2)
+        pipe.enable_freeu(*args.freeu)
     scheduler = getattr(args, "scheduler", "unipc")
     simple = {"ddim": P.DDIMScheduler, "euler": P.EulerDiscreteScheduler, "euler_a": P.EulerAncestralDiscreteScheduler,
               "lms": P.LMSDiscreteScheduler, "pndm": P.PNDMScheduler}
@@ -298,6 +300,8 @@ def build_parser():
     p.add_argument("--pose_det_num_classes", type=int, default=80, help="classes of --pose_det_weights (COCO: 80; class 0 is the person)")
     p.add_argument("--scheduler", choices=("unipc", "ddim", "dpmpp", "dpmpp_2m", "dpmpp_2m_karras", "dpmpp_2m_sde", "euler", "euler_a", "lms", "pndm"),
                    default="unipc")
+    p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
+                   help="FreeU in the two lowest-resolution decoder blocks (pipe.enable_freeu; e.g. 0.9 0.2 1.2 1.4); default: off")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage2_checkpoints/512")
     return p
 

@@ -58,7 +58,9 @@ def inference(args, rank, select_test_datas):
     pipe.unet = P.UNet2DConditionModel.from_pretrained(args.pretrained_model_name_or_path, subfolder="unet", in_channels=8,
                                                        low_cpu_mem_usage=False, ignore_mismatched_sizes=True).to(device)
     pipe.unet.load_state_dict(unet_dict)
-    sched_cls = {"unipc": P.UniPCMultistepScheduler, "ddim": P.DDIMScheduler, "dpmpp": P.DPMSolverMultistepScheduler,
+    if getattr(args, "freeu", None):   # opt-in (no reference counterpart in this driver): pipe.enable_freeu(s1, s2, b1, b2)
+        pipe.enable_freeu(*args.freeu)
+    sched_cls ={"unipc": P.UniPCMultistepScheduler, "ddim": P.DDIMScheduler, "dpmpp": P.DPMSolverMultistepScheduler,
                  "euler": P.EulerDiscreteScheduler, "euler_a": P.EulerAncestralDiscreteScheduler, "lms": P.LMSDiscreteScheduler,
                  "pndm": P.PNDMScheduler}[getattr(args, "scheduler", "unipc")]   # (unipc: the reference driver's choice)
     pipe.scheduler = sched_cls.from_config(pipe.scheduler.config)
@@ -143,6 +145,8 @@ def build_parser():
     p.add_argument("--preprocess_device", choices=("host", "gpu"), default="host",
                    help="where the inputs are resized, normalised and turned into CLIP pixels: host (PIL / CLIPImageProcessor, as the reference) or "
                         "gpu (pcdms_amd.preprocess, the same bytes)")
+    p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
+                   help="FreeU in the two lowest-resolution decoder blocks (pipe.enable_freeu; e.g. 0.9 0.2 1.2 1.4); default: off")
     p.add_argument("--weights_name", type=str, default="./Checkpoints/stage3_checkpoints/512")
     return p
 
