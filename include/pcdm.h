@@ -114,7 +114,10 @@ typedef struct pcdm_gemm_params {
     int32_t split_k;   /* > 1: split K over split_k workgroups per tile (PCDM_EPI_STORE only); partial sums in ws */
     float* ws;         /* fp32 workspace, >= split_k * M * Npad floats */
     int64_t ws_floats;
-    int64_t ldw;       /* row stride of W in elements (0 -> K); lets an activation slice act as the [N,K] operand */
+    int64_t ldw;       /* row stride of W in elements (0 -> K); lets an activation slice act as the [N,K] operand.  As for a packed W, ALL Npad
+                          rows are read (rows >= N only enter output columns that are never stored, so they may hold anything): the slice
+                          must have (Npad - 1) * ldw + K readable elements behind w -- a caller whose tensor ends earlier allocates the
+                          difference (tests/test_operand_containment.py runs the call at exactly this extent) */
     int32_t no_pad_lo; /* conv: 1 = zero padding at the bottom/right only (taps start AT the output pixel): the VAE
                           encoder's Downsample2D(padding=0) + F.pad(0,1,0,1); 0 = symmetric padding 1 */
     int32_t tile;      /* 0 = heuristic; 1..26 = explicit tile configuration (gemm.hip dispatch_tile; 22 / 23 = the 176-row tiles), 31..36 = the A-in-registers thin-K

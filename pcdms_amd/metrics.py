@@ -217,7 +217,7 @@ class LPIPS:
             t = {k: v.to(device) for k, v in self.packed.items()}
             w = _lib.LpipsWeights()
             for l in range(5):
-                w.conv_w[l], w.conv_b[l], w.lin[l] = t[f"conv{l}.w"].data_ptr(), t[f"conv{l}.bias"].data_ptr(), t[f"lin{l}"].data_ptr()
+                w.conv_w[l], w.conv_b[l], w.lin[l] = ops._ptr(t[f"conv{l}.w"]), ops._ptr(t[f"conv{l}.bias"]), ops._ptr(t[f"lin{l}"])
             self._dev[key] = (t, w)
         return self._dev[key][1]
 
@@ -350,7 +350,7 @@ class InceptionV3Features:
             t = [{k: v.to(device) for k, v in p.items()} for p in self.packed]
             w = _lib.InceptionWeights()
             for i, p in enumerate(t):
-                w.w[i], w.bias[i] = p["w"].data_ptr(), p["bias"].data_ptr()
+                w.w[i], w.bias[i] = ops._ptr(p["w"]), ops._ptr(p["bias"])
             self._dev[key] = (t, w)
         return self._dev[key][1]
 

@@ -52,6 +52,13 @@ def _c(t: torch.Tensor, dtype) -> torch.Tensor:
     return t
 
 
+def _cn(t: Optional[torch.Tensor], dtype, numel: int, what: str) -> Optional[torch.Tensor]:
+    """an optional operand the kernel indexes as ``numel`` contiguous elements of ``dtype`` (more is fine: a table, a wider buffer)"""
+    if t is not None:
+        assert t.dtype == dtype and t.is_contiguous() and t.numel() >= numel, (what, t.dtype, dtype, t.is_contiguous(), t.numel(), numel)
+    return t
+
+
 # ------------------------------------------------------------------------------------ GEMM tiles, tuner and workspace state
 ROWGEMM_TILES = (31, 32, 33, 34, 35, 36)   # rowgemm.hip (K = 320): id -> (BM, BN) below
 STATS_TILES = (2, 4, 5, 6, 7, 8, 10, 18)   # gemm_ext.hip EXT = 3: the tiles whose STORE epilogue can also write LayerNorm partials (row_stats)
@@ -152,7 +159,9 @@ def groupnorm(x1: Union[torch.Tensor, "DeferredGemm"], x2: Optional[torch.Tensor
     C1 = x1.shape[-1]
     C2 = 0 if x2 is None else x2.shape[-1]
     _c(out, BF16); _c(gamma, torch.float32); _c(beta, torch.float32)
-    assert ws.numel() >= _lib.lib().pcdm_groupnorm_ws_floats(B, C1 + C2)
+    assert out.numel() == B * HW * (C1 + C2) and gamma.numel() >= C1 + C2 and beta.numel() >= C1 + C2
+    assert x2 is None or (_c(x2, BF16).numel() == B * HW * C2)
+    assert _c(ws, torch.float32).numel() >= _lib.lib().pcdm_groupnorm_ws_floats(B, C1 + C2)
     if isinstance(x1, DeferredGemm):
         d = x1
         assert d.M == B * HW and d.N == C1 and (d.rowvec is None or d.rpb == HW), "rowvec rows must be the GroupNorm's batch entries"
@@ -165,7 +174,7 @@ def groupnorm(x1: Union[torch.Tensor, "DeferredGemm"], x2: Optional[torch.Tensor
         fn, call = "pcdm_groupnorm_splitk", lambda: _lib.lib().pcdm_groupnorm_splitk(
             C.byref(sp), _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta), int(silu), _ptr(out), _ptr(ws), _stream(out))
     else:
-        _c(x1, BF16)
+        assert _c(x1, BF16).numel() == B * HW * C1
         fn, call = "pcdm_groupnorm", lambda: _lib.lib().pcdm_groupnorm(
             _ptr(x1), C1, _ptr(x2), C2, B, HW, groups, eps, _ptr(gamma), _ptr(beta), int(silu), _ptr(out), _ptr(ws), _stream(x1))
     # algorithmic bytes: the tensor read once + written once
@@ -176,6 +185,8 @@ def groupnorm(x1: Union[torch.Tensor, "DeferredGemm"], x2: Optional[torch.Tensor
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:
     rows, Cc = x.shape
     _c(x, BF16); _c(out, BF16)
+    assert out.numel() == x.numel()
+    _cn(gamma, torch.float32, Cc, "gamma"); _cn(beta, torch.float32, Cc, "beta")
     _chk(_launch(x, lambda: _lib.lib().pcdm_layernorm(_ptr(x), _ptr(out), rows, Cc, eps, _ptr(gamma), _ptr(beta), _stream(x)),
                  "layernorm", 2.0 * rows * Cc * 2, (rows, Cc)), "pcdm_layernorm")
     return out
@@ -279,6 +290,7 @@ def pack_upsample_phases(w: torch.Tensor, bias: Optional[torch.Tensor], device) 
 def pixel_shuffle2(x: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, Cc: int) -> torch.Tensor:
     """[B*H*W, 4*Cc] (phase-major columns) -> NHWC [B, 2H, 2W, Cc] (as [B*2H*2W, Cc]): the second half of the phase-decomposed upsample convolution."""
     assert x.dtype == BF16 and out.dtype == BF16 and x.is_contiguous() and out.is_contiguous() and x.numel() == out.numel() == B * H * W * 4 * Cc
+    assert Cc % 8 == 0 and x.device == out.device, (Cc, x.device, out.device)
     _chk(_lib.lib().pcdm_pixel_shuffle2(_ptr(x), _ptr(out), B, H, W, Cc, _stream(x)), "pcdm_pixel_shuffle2")
     return out
 
@@ -297,6 +309,11 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, skip_out: torch.Tensor, B: i
     assert all(t.dtype == BF16 and t.is_contiguous() and t.dim() == 2 and t.shape[0] == B * H * W for t in (hidden, ho, skip, skip_out))
     assert ho.shape == hidden.shape and skip_out.shape == skip.shape
     C1, C2 = hidden.shape[1], skip.shape[1]
+    need = freeu_ws_bytes(B, H, W, C1, C2)
+    assert need >= 0, (B, H, W, C1, C2)
+    if need > 0 or ws is not None:
+        assert ws is not None and ws.is_contiguous() and ws.numel() * ws.element_size() >= need and ws.device == skip.device, \
+            f"pcdm_freeu needs a workspace of {need} bytes at this shape"
     call = lambda: _lib.lib().pcdm_freeu(_ptr(hidden), _ptr(ho), _ptr(skip), _ptr(skip_out), B, H, W, C1, C2, float(b), float(s), _ptr(ws),  # noqa: E731
                                          _stream(skip))
     _chk(_launch(skip, call, "freeu", 14.0 * B * H * W * C2, (B, H, W, C1, C2)), "pcdm_freeu")
@@ -476,11 +493,11 @@ def gemm(a: torch.Tensor, pw: PackedWeight, out: torch.Tensor, *, a2: Optional[t
     deferred = None
     if split > 1:
         ws = _splitk_ws(a.device, split * M * pw.Npad)
-        p.split_k, p.ws, p.ws_floats = split, ws.data_ptr(), ws.numel()
+        p.split_k, p.ws, p.ws_floats = split, _ptr(ws), ws.numel()
         if defer_reduce is not None and DEFER_SPLITK and epilogue == EPI_STORE and act == ACT_NONE and (residual is None or res_mod in (0, M)) \
                 and (rowvec is None or (rows_per_batch and M % rows_per_batch == 0)) and out.is_contiguous() and out.shape == (M, pw.N):
             p.defer_reduce = 1
-            deferred = DeferredGemm(part=ws.data_ptr(), split_k=split, M=M, N=pw.N, Npad=pw.Npad, bias=p.bias, rowvec=p.rowvec,
+            deferred = DeferredGemm(part=_ptr(ws), split_k=split, M=M, N=pw.N, Npad=pw.Npad, bias=p.bias, rowvec=p.rowvec,
                                     ldrv=p.ldrv if rowvec is not None else 0, rowvec_step=p.rowvec_step, rowvec_step_stride=p.rowvec_step_stride,
                                     rowvec_step_count=p.rowvec_step_count, step_error=p.step_error,
                                     rpb=p.rows_per_batch, residual=p.residual, ldr=p.ldr, out=out,
@@ -643,7 +660,7 @@ def _autotune(p: GemmParams, stream, pw: PackedWeight, epilogue: int, device, ou
             p.tile = tile
             if sk > 1:
                 ws = _splitk_ws(device, sk * p.M * pw.Npad)
-                p.split_k, p.ws, p.ws_floats = sk, ws.data_ptr(), ws.numel()
+                p.split_k, p.ws, p.ws_floats = sk, _ptr(ws), ws.numel()
             else:
                 p.split_k, p.ws, p.ws_floats = 0, None, 0
             if fn(C.byref(p), stream) != 0:   # configuration not valid for this N / epilogue
@@ -741,6 +758,7 @@ def quantize_fp8(x: torch.Tensor, out: torch.Tensor, cols: Optional[int] = None,
     assert x.dtype == BF16 and out.dtype == FP8 and x.stride(-1) == 1 and out.stride(-1) == 1 and x.dim() == 2 and out.dim() == 2
     rows = x.shape[0]
     cols = cols if cols is not None else x.shape[1]
+    assert out.shape[0] == rows and 1 <= cols <= x.shape[1] and cols <= out.shape[1] and out.shape[1] % 8 == 0, (x.shape, out.shape, cols)
     _chk(_lib.lib().pcdm_quantize_fp8(_ptr(x), _ptr(out), rows, cols, out.shape[1], x.stride(0), out.stride(0), float(scale), _stream(x)),
          "pcdm_quantize_fp8")
     return out
@@ -763,7 +781,9 @@ def flash_attn_fp8(q: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, out: to
 def timestep_embedding(t_dev: torch.Tensor, step_dev: Optional[torch.Tensor], out: torch.Tensor, flip: bool = True,
                        shift: float = 0.0) -> torch.Tensor:
     """t_dev: int64 or float32 device table (a float table keeps its fractional timesteps: ``pcdm_timestep_embedding_f32``)."""
-    assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and out.dtype == torch.float32
+    assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and t_dev.numel() >= 1
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2
+    _cn(step_dev, torch.int32, 1, "step_dev")
     B, dim = out.shape
     fn = _lib.lib().pcdm_timestep_embedding if t_dev.dtype == torch.int64 else _lib.lib().pcdm_timestep_embedding_f32
     _chk(fn(_ptr(t_dev), _ptr(step_dev), _ptr(out), B, dim, int(flip), shift, _stream(out)), "pcdm_timestep_embedding")
@@ -794,18 +814,31 @@ def small_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     _c(x, torch.float32); _c(w, BF16); _c(out, torch.float32)
     B, K = x.shape
     N = w.shape[0]
+    assert tuple(w.shape) == (N, K) and tuple(out.shape) == (B, N), (x.shape, w.shape, out.shape)
+    _cn(bias, torch.float32, N, "bias")
+    assert add is None or (_c(add, torch.float32).numel() == B * N), "add is fp32 [B, N]"
     _chk(_lib.lib().pcdm_small_linear(_ptr(x), _ptr(w), _ptr(bias), _ptr(add), _ptr(out), B, K, N, int(act_in),
                                       int(act_out), _stream(x)), "pcdm_small_linear")
     return out
 
 
+def _assemble_operands(latents, rep, mask, masked, out):
+    """the extents ``pcdm_assemble_input(_ex)`` indexes (the C call is handed no sizes of mask / masked / out)"""
+    assert latents.dim() == 4 and latents.shape[1] == 4 and rep >= 1, (latents.shape, rep)
+    N, _, h, w = latents.shape
+    _c(latents, torch.float32); _c(masked, torch.float32); _c(out, BF16)
+    assert masked.dim() == 4 and tuple(masked.shape[1:]) == (4, h, w) and masked.shape[0] in (1, rep * N), (masked.shape, latents.shape, rep)
+    assert out.dim() == 4 and tuple(out.shape[:3]) == (rep * N, h, w) and out.shape[3] % 8 == 0 and out.shape[3] >= 16, (out.shape, latents.shape, rep)
+    if mask is not None:
+        _c(mask, torch.float32)
+        assert mask.dim() == 4 and tuple(mask.shape[1:]) == (1, h, w) and mask.shape[0] in (1, rep * N), (mask.shape, latents.shape, rep)
+
+
 def assemble_input(latents: torch.Tensor, rep: int, mask: Optional[torch.Tensor], masked: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """latents fp32 [N,4,h,w]; mask [1|rep*N,1,h,w] or None (no mask channel: stage 3); masked [1|rep*N,4,h,w]
     -> out bf16 [rep*N,h,w,cpad]."""
+    _assemble_operands(latents, rep, mask, masked, out)
     N, _, h, w = latents.shape
-    _c(latents, torch.float32); _c(masked, torch.float32); _c(out, BF16)
-    if mask is not None:
-        _c(mask, torch.float32)
     cpad = out.shape[-1]
     _chk(_lib.lib().pcdm_assemble_input(_ptr(latents), N, rep, _ptr(mask), 1 if mask is None else mask.shape[0], _ptr(masked),
                                         masked.shape[0], _ptr(out), h, w, cpad, _stream(out)), "pcdm_assemble_input")
@@ -817,19 +850,14 @@ def assemble_input_ex(latents: torch.Tensor, rep: int, mask: Optional[torch.Tens
                       step_error: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``assemble_input`` with ``scheduler.scale_model_input`` folded in (pcdm_assemble_input_ex): the latent channels are multiplied by
     ``scale_tab[*step_dev, scale_col]`` (fp32 device table [rows, stride]) before their rounding to bf16; ``scale_tab=None``: ``assemble_input``."""
+    _assemble_operands(latents, rep, mask, masked, out)
     N, _, h, w = latents.shape
-    _c(latents, torch.float32); _c(masked, torch.float32); _c(out, BF16)
-    if mask is not None:
-        _c(mask, torch.float32)
     rows = stride = 1
     if scale_tab is not None:
         _c(scale_tab, torch.float32)
         assert scale_tab.dim() == 2 and 0 <= scale_col < scale_tab.shape[1]
         rows, stride = scale_tab.shape
-    if step_dev is not None:
-        assert step_dev.dtype == torch.int32
-    if step_error is not None:
-        assert step_error.dtype == torch.int32
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
     _chk(_lib.lib().pcdm_assemble_input_ex(_ptr(latents), N, rep, _ptr(mask), 1 if mask is None else mask.shape[0], _ptr(masked),
                                            masked.shape[0], _ptr(out), h, w, out.shape[-1], _ptr(scale_tab), stride, int(scale_col), rows,
                                            _ptr(step_dev), _ptr(step_error), _stream(out)), "pcdm_assemble_input_ex")
@@ -843,12 +871,13 @@ def nchw_to_nhwc_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None, cpad:
     cpad = cpad or _round_up(Cc, 8)
     if out is None:
         out = torch.empty(B, H, W, cpad, dtype=BF16, device=x.device)
-    assert out.shape[-1] == cpad
+    assert out.shape[-1] == cpad and _c(out, BF16).numel() == B * H * W * cpad
     _chk(_lib.lib().pcdm_nchw_f32_to_nhwc_bf16(_ptr(x), _ptr(out), B, Cc, cpad, H * W, _stream(x)), "nchw_to_nhwc")
     return out
 
 
 def nhwc_bf16_to_nchw(x: torch.Tensor, B: int, Cc: int, H: int, W: int) -> torch.Tensor:
+    assert x.numel() == B * H * W * Cc, (x.shape, B, Cc, H, W)
     out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=x.device)
     _chk(_lib.lib().pcdm_nhwc_bf16_to_nchw_f32(_ptr(_c(x, BF16)), _ptr(out), B, Cc, H * W, _stream(x)), "nhwc_to_nchw")
     return out
@@ -858,6 +887,7 @@ def f32_to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     x = _c(x, torch.float32)
     if out is None:
         out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    assert _c(out, BF16).numel() == x.numel()
     _chk(_lib.lib().pcdm_f32_to_bf16(_ptr(x), _ptr(out), x.numel(), _stream(x)), "f32_to_bf16")
     return out
 
@@ -867,6 +897,12 @@ def cfg_step(eps: torch.Tensor, cfg: bool, g: float, x: Optional[torch.Tensor], 
              noise: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None) -> None:
     n = eps.numel() // (2 if cfg else 1)
     _c(eps, torch.float32)
+    assert eps.numel() == (2 * n if cfg else n) and n >= 1
+    for what, t in (("x", x), ("noise", noise), ("x_prev", x_prev), ("eps_out", eps_out)):
+        assert t is None or _c(t, torch.float32).numel() == n, (what, t.numel(), n)
+    assert (x_prev is None) == (x is None) == (coef is None), "x, x_prev and coef come together (eps_out alone: the CFG combine only)"
+    _cn(coef, torch.float32, 4, "coef"); _cn(step_dev, torch.int32, 1, "step_dev")
+    assert coef is None or coef.numel() % 4 == 0
     _chk(_lib.lib().pcdm_cfg_step(_ptr(eps), int(cfg), g, _ptr(x), _ptr(noise), _ptr(x_prev), _ptr(eps_out),
                                   _ptr(coef), _ptr(step_dev), n, _stream(eps)), "pcdm_cfg_step")
 
@@ -878,6 +914,7 @@ def unipc_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torc
     for t in (eps, x, m1, m2, last, coef):
         _c(t, torch.float32)
     assert eps.numel() == (2 * n if cfg else n) and m1.numel() == m2.numel() == last.numel() == n and coef.shape[-1] == 12
+    _cn(step_dev, torch.int32, 1, "step_dev")
     _chk(_lib.lib().pcdm_unipc_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(m2), _ptr(last), _ptr(coef),
                                     _ptr(step_dev), n, _stream(x)), "pcdm_unipc_step")
 
@@ -890,6 +927,7 @@ def dpmpp_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torc
     for t in (eps, x, m1, coef):
         _c(t, torch.float32)
     assert eps.numel() == (2 * n if cfg else n) and m1.numel() == n and coef.shape[-1] == 8
+    _cn(step_dev, torch.int32, 1, "step_dev")
     if noise_all is not None:
         assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
     _chk(_lib.lib().pcdm_dpmpp_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(noise_all), _ptr(coef),
@@ -913,10 +951,7 @@ def multistep_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, xs: 
     assert len({t.data_ptr() for t in (x, xs, h1, h2, h3)}) == 5, "the five state slots are distinct buffers"
     if noise_all is not None:
         assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
-    if step_dev is not None:
-        assert step_dev.dtype == torch.int32
-    if step_error is not None:
-        assert step_error.dtype == torch.int32
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
     _chk(_lib.lib().pcdm_multistep_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(xs), _ptr(h1), _ptr(h2), _ptr(h3), _ptr(noise_all),
                                         _ptr(coef), coef.shape[0], _ptr(step_dev), _ptr(step_error), n, _stream(x)), "pcdm_multistep_step")
 
@@ -941,6 +976,7 @@ def unclip_step_dev(pred: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, no
     _c(pred, torch.float32); _c(x, torch.float32); _c(coef, torch.float32)
     n = x.numel()
     assert pred.numel() == (2 * n if cfg else n) and coef.shape[-1] == 8
+    _cn(step_dev, torch.int32, 1, "step_dev")
     if noise_all is not None:
         assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
     _chk(_lib.lib().pcdm_unclip_step_dev(_ptr(pred), int(cfg), float(g), _ptr(x), _ptr(noise_all), _ptr(coef), _ptr(step_dev), n,
@@ -953,7 +989,8 @@ def lincomb(out: torch.Tensor, xs: Sequence[torch.Tensor], cs: Sequence[float]) 
     for t in xs:
         _c(t, torch.float32)
         assert t.numel() == out.numel()
-    arr = (C.c_void_p * n)(*[t.data_ptr() for t in xs])
+    _c(out, torch.float32)
+    arr = (C.c_void_p * n)(*[_ptr(t) for t in xs])
     carr = (C.c_float * n)(*[float(c) for c in cs])
     _chk(_lib.lib().pcdm_lincomb(_ptr(out), n, arr, carr, out.numel(), _stream(out)), "pcdm_lincomb")
     return out
@@ -963,6 +1000,7 @@ def rescale_noise_cfg(cfg_eps: torch.Tensor, text_eps: torch.Tensor, out: torch.
     """fp32 [N, ...] tensors; per-sample std matching (ref stage2_inpaint_pipeline.py:52-63)."""
     _c(cfg_eps, torch.float32); _c(text_eps, torch.float32); _c(out, torch.float32)
     N = cfg_eps.shape[0]
+    assert text_eps.numel() == cfg_eps.numel() == out.numel()
     _chk(_lib.lib().pcdm_rescale_noise_cfg(_ptr(cfg_eps), _ptr(text_eps), _ptr(out), N, cfg_eps.numel() // N,
                                            float(guidance_rescale), _stream(out)), "pcdm_rescale_noise_cfg")
     return out
@@ -972,12 +1010,34 @@ def softmax_rows(s: torch.Tensor, out: torch.Tensor, scale: float) -> torch.Tens
     """fp32 [rows, cols] -> bf16 [rows, cols] = softmax(scale * s, dim=-1)."""
     assert s.dtype == torch.float32 and out.dtype == BF16 and s.stride(1) == 1 and out.stride(1) == 1
     rows, cols = s.shape
+    assert out.dim() == 2 and out.shape[0] == rows and out.shape[1] >= cols, (s.shape, out.shape)
     _chk(_lib.lib().pcdm_softmax_rows(_ptr(s), _ptr(out), rows, cols, s.stride(0), out.stride(0), float(scale), _stream(s)),
          "pcdm_softmax_rows")
     return out
 
 
+def gaussian_sample(moments: torch.Tensor, noise: torch.Tensor, out: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """moments fp32 [B, 2 zc, H, W] (mean | logvar), noise fp32 [B, zc, H, W] -> out = (mean + exp(0.5 clamp(logvar)) noise) scale
+    (include/pcdm.h: pcdm_gaussian_sample)."""
+    _c(moments, torch.float32); _c(noise, torch.float32); _c(out, torch.float32)
+    B, c2 = int(moments.shape[0]), int(moments.shape[1])
+    assert moments.dim() >= 3 and c2 % 2 == 0 and noise.numel() == out.numel() == moments.numel() // 2 and noise.shape[0] == B, (moments.shape, noise.shape, out.shape)
+    HW = moments.numel() // (B * c2)
+    _chk(_lib.lib().pcdm_gaussian_sample(_ptr(moments), _ptr(noise), _ptr(out), B, c2 // 2, HW, float(scale), _stream(out)), "pcdm_gaussian_sample")
+    return out
+
+
+def image_to_uint8(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """x fp32 [B, cstride, H, W] (the first 3 channels) -> out uint8 [B, H, W, 3]: VaeImageProcessor.postprocess (include/pcdm.h: pcdm_image_to_uint8)."""
+    _c(x, torch.float32); _c(out, torch.uint8)
+    B, cs = int(x.shape[0]), int(x.shape[1])
+    assert x.dim() == 4 and cs >= 3 and tuple(out.shape) == (B, x.shape[2], x.shape[3], 3), (x.shape, out.shape)
+    _chk(_lib.lib().pcdm_image_to_uint8(_ptr(x), _ptr(out), B, cs, int(x.shape[2] * x.shape[3]), _stream(out)), "pcdm_image_to_uint8")
+    return out
+
+
 def advance_step(step_dev: torch.Tensor) -> None:
+    _cn(step_dev, torch.int32, 1, "step_dev")
     _chk(_lib.lib().pcdm_advance_step(_ptr(step_dev), _stream(step_dev)), "pcdm_advance_step")
 
 
@@ -1237,6 +1297,7 @@ def fid_finalize(total: torch.Tensor, gram: torch.Tensor, n: int):
     (include/pcdm.h: pcdm_fid_finalize)."""
     _c(total, torch.float64); _c(gram, torch.float64)
     D = int(total.shape[0])
+    assert tuple(total.shape) == (D,) and tuple(gram.shape) == (D, D) and gram.device == total.device, (total.shape, gram.shape)
     mu, sigma = torch.empty_like(total), torch.empty_like(gram)
     _chk(_lib.lib().pcdm_fid_finalize(_ptr(total), _ptr(gram), int(n), D, _ptr(mu), _ptr(sigma), _stream(total)), "pcdm_fid_finalize")
     return mu, sigma

@@ -293,16 +293,16 @@ class DWPoseEstimator:
             for i, (_, co, nb, ident, spp) in enumerate(self.stages):
                 cfg.out[i], cfg.blocks[i], cfg.identity[i], cfg.spp[i] = co, nb, int(ident), int(spp)
             convs, dws = self._conv_order()
-            arr = lambda names, key: (C.c_void_p * len(names))(*[w[n][key].data_ptr() for n in names])   # noqa: E731
+            arr = lambda names, key: (C.c_void_p * len(names))(*[ops._ptr(w[n][key]) for n in names])   # noqa: E731
             keep = [arr(convs, "w"), arr(convs, "bias"), arr(dws, "w"), arr(dws, "bias")]
             wt = _lib.DWPoseWeights(n_conv=len(convs), n_dw=len(dws))
             wt.conv_w, wt.conv_b, wt.dw_w, wt.dw_b = (C.cast(a, C.POINTER(C.c_void_p)) for a in keep)
             for i, (_, _, _, _, spp) in enumerate(self.stages):
                 fc = w[f"backbone.stage{i + 1}.{2 if spp else 1}.attention.fc"]
-                wt.fc_w[i], wt.fc_b[i] = fc["w"].data_ptr(), fc["bias"].data_ptr()
-            wt.mlp_g, wt.ln_g = w["head.mlp.0.g"].data_ptr(), w["head.gau.ln.g"].data_ptr()
-            wt.gamma, wt.beta, wt.res_scale = w["head.gau.gamma"].data_ptr(), w["head.gau.beta"].data_ptr(), w["head.gau.res_scale.scale"].data_ptr()
-            wt.flip_idx = None if w["flip"] is None else w["flip"].data_ptr()
+                wt.fc_w[i], wt.fc_b[i] = ops._ptr(fc["w"]), ops._ptr(fc["bias"])
+            wt.mlp_g, wt.ln_g = ops._ptr(w["head.mlp.0.g"]), ops._ptr(w["head.gau.ln.g"])
+            wt.gamma, wt.beta, wt.res_scale = ops._ptr(w["head.gau.gamma"]), ops._ptr(w["head.gau.beta"]), ops._ptr(w["head.gau.res_scale.scale"])
+            wt.flip_idx = ops._ptr(w["flip"])
             w["c_args"] = (cfg, wt, keep)
         return w["c_args"][0], w["c_args"][1]
 
@@ -587,7 +587,7 @@ class PersonDetector:
             for i, (_, co, nb, _, _) in enumerate(self.stages):
                 cfg.out[i], cfg.blocks[i] = co, nb
             convs = self._conv_order()
-            keep = [(C.c_void_p * len(convs))(*[w[n][key].data_ptr() for n in convs]) for key in ("w", "bias")]
+            keep = [(C.c_void_p * len(convs))(*[ops._ptr(w[n][key]) for n in convs]) for key in ("w", "bias")]
             wt = _lib.DetectWeights(n_conv=len(convs))
             wt.conv_w, wt.conv_b = (C.cast(a, C.POINTER(C.c_void_p)) for a in keep)
             w["c_args"] = (cfg, wt, keep)

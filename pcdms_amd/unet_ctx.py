@@ -62,18 +62,18 @@ class UNetContext:
 
     def _set_w(self, name: str, pw: ops.PackedWeight):
         self._keep.append(pw)
-        self._chk(_lib.lib().pcdm_unet_set_weight(self._h, name.encode(), pw.w.data_ptr(), None if pw.bias is None else pw.bias.data_ptr(),
-                                                  None if pw.wsum is None else pw.wsum.data_ptr(), pw.N, pw.K, pw.Npad, pw.cin), name)
+        self._chk(_lib.lib().pcdm_unet_set_weight(self._h, name.encode(), ops._ptr(pw.w), ops._ptr(pw.bias),
+                                                  ops._ptr(pw.wsum), pw.N, pw.K, pw.Npad, pw.cin), name)
 
     def _set_small(self, name: str, wb):
         w, b = wb
         self._keep.append(wb)
-        self._chk(_lib.lib().pcdm_unet_set_weight(self._h, name.encode(), w.data_ptr(), b.data_ptr(), None, w.shape[0], w.shape[1], w.shape[0], 0), name)
+        self._chk(_lib.lib().pcdm_unet_set_weight(self._h, name.encode(), ops._ptr(w), ops._ptr(b), None, w.shape[0], w.shape[1], w.shape[0], 0), name)
 
     def _set_v(self, name: str, gb):
         for sfx, t in zip(("weight", "bias"), gb):
             self._keep.append(t)
-            self._chk(_lib.lib().pcdm_unet_set_vector(self._h, f"{name}.{sfx}".encode(), t.data_ptr(), t.numel()), name)
+            self._chk(_lib.lib().pcdm_unet_set_vector(self._h, f"{name}.{sfx}".encode(), ops._ptr(t), t.numel()), name)
 
     def _register(self):
         W, u = self.unet._w, self.unet
@@ -134,7 +134,7 @@ class UNetContext:
             if n <= 0:
                 raise RuntimeError("pcdm_unet_workspace_bytes failed")
             ws = torch.empty(n, dtype=torch.uint8, device=self.unet.device)
-            self._chk(_lib.lib().pcdm_unet_workspace_init(self._h, B, h, w, L, ws.data_ptr(), ops._stream(ws)), "pcdm_unet_workspace_init")
+            self._chk(_lib.lib().pcdm_unet_workspace_init(self._h, B, h, w, L, ops._ptr(ws), ops._stream(ws)), "pcdm_unet_workspace_init")
             self._ws[key] = ws
         return ws
 
@@ -150,10 +150,10 @@ class UNetContext:
         pose = None if my_pose_cond is None else my_pose_cond.to(dev, torch.float32).contiguous()
         pose_b = 0 if pose is None else pose.shape[0]
         ws = self.workspace(B, h, w, L)
-        self._chk(_lib.lib().pcdm_unet_prepare_conditioning(self._h, B, h, w, L, ehs.data_ptr(), None if cl is None else cl.data_ptr(),
-                                                            None if pose is None else pose.data_ptr(), pose_b, int(zero_ctx_batches),
-                                                            ws.data_ptr(), ops._stream(ws)), "pcdm_unet_prepare_conditioning")
-        self._chk(_lib.lib().pcdm_unet_set_shared_cfg_input(self._h, ws.data_ptr(), int(bool(shared_cfg_input))), "pcdm_unet_set_shared_cfg_input")
+        self._chk(_lib.lib().pcdm_unet_prepare_conditioning(self._h, B, h, w, L, ops._ptr(ehs), ops._ptr(cl),
+                                                            ops._ptr(pose), pose_b, int(zero_ctx_batches),
+                                                            ops._ptr(ws), ops._stream(ws)), "pcdm_unet_prepare_conditioning")
+        self._chk(_lib.lib().pcdm_unet_set_shared_cfg_input(self._h, ops._ptr(ws), int(bool(shared_cfg_input))), "pcdm_unet_set_shared_cfg_input")
         self._L = L
         return pose_b
 
@@ -170,7 +170,7 @@ class UNetContext:
         if tab is None:
             tab = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.unet.device)
         ws = self.workspace(B, h, w, self._L)
-        self._chk(fn(self._h, t_dev.data_ptr(), n, tab.data_ptr(), ws.data_ptr(), ops._stream(ws)), "pcdm_unet_prepare_timesteps")
+        self._chk(fn(self._h, ops._ptr(t_dev), n, ops._ptr(tab), ops._ptr(ws), ops._stream(ws)), "pcdm_unet_prepare_timesteps")
 
     def step_overflow(self, B: int, h: int, w: int) -> bool:
         """``pcdm_unet_step_overflow``: did a forward on this shape's workspace find the device step counter outside the prepared time table?
@@ -178,7 +178,7 @@ class UNetContext:
         import ctypes as C
         ws = self.workspace(B, h, w, self._L)
         flag = C.c_int(0)
-        self._chk(_lib.lib().pcdm_unet_step_overflow(self._h, ws.data_ptr(), C.byref(flag), ops._stream(ws)), "pcdm_unet_step_overflow")
+        self._chk(_lib.lib().pcdm_unet_step_overflow(self._h, ops._ptr(ws), C.byref(flag), ops._stream(ws)), "pcdm_unet_step_overflow")
         return bool(flag.value)
 
     @torch.no_grad()
@@ -192,6 +192,6 @@ class UNetContext:
         ws = self.workspace(B, h, w, self._L)
         if out is None:
             out = torch.empty(B, self.unet.config.out_channels, h, w, dtype=torch.float32, device=x_in.device)
-        self._chk(fn(self._h, x_in.data_ptr(), t_dev.data_ptr(), None if step_dev is None else step_dev.data_ptr(),
-                     B, h, w, self._L, pose_b, ws.data_ptr(), out.data_ptr(), ops._stream(x_in)), "pcdm_unet_forward")
+        self._chk(fn(self._h, ops._ptr(x_in), ops._ptr(t_dev), ops._ptr(step_dev),
+                     B, h, w, self._L, pose_b, ops._ptr(ws), ops._ptr(out), ops._stream(x_in)), "pcdm_unet_forward")
         return out

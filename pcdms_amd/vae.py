@@ -39,9 +39,7 @@ class DiagonalGaussianDistribution:
             noise = torch.randn((B, c2 // 2, h, w), generator=generator, device=gdev, dtype=torch.float32)
         noise = noise.to(self.parameters.device, torch.float32).contiguous()
         out = torch.empty_like(noise)
-        ops._chk(_lib.lib().pcdm_gaussian_sample(self.parameters.data_ptr(), noise.data_ptr(), out.data_ptr(), B, c2 // 2,
-                                                 h * w, 1.0, ops._stream(out)), "pcdm_gaussian_sample")
-        return out
+        return ops.gaussian_sample(self.parameters, noise, out, 1.0)
 
     def mode(self) -> torch.Tensor:
         return self.mean
@@ -278,9 +276,7 @@ class AutoencoderKL(HipModel):
         base = self._decode_buf(z)
         B, _, H, W = base.shape
         out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self._device)
-        ops._chk(_lib.lib().pcdm_image_to_uint8(base.data_ptr(), out.data_ptr(), B, base.shape[1], H * W, ops._stream(out)),
-                 "pcdm_image_to_uint8")
-        return out
+        return ops.image_to_uint8(base, out)
 
 
 def _param_shapes(cfg) -> Iterator[Tuple[str, Tuple[int, ...]]]:
