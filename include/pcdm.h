@@ -609,12 +609,48 @@ int pcdm_ssim_box(const void* cand, int N, int Hc, int Wc, const int32_t* cand_w
  *   [M, Hs, Ws, 3] -> dst [M, Hd, Wd, 3].  Per axis scale = 1.0 / ((double)n_out / (double)n_in), f = (float)((d + 0.5) * scale - 0.5), s = floor(f),
  *   t = f - s in fp32; weights w0 = rint((1 - t) * 2048), w1 = rint(t * 2048).  Horizontally an index outside [0, n_in - 2] is clamped and its
  *   t set to 0; vertically the two rows s, s + 1 are clamped into the image and t is kept.  S = src[s] w0 + src[s + 1] w1 in int per row,
- *   out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Equal sizes copy.  One launch; -1 for non-positive sizes or 2^31 bytes. */
+ *   out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Equal sizes copy.  One launch; -1 for non-positive sizes or 2^31 bytes.
+ * pcdm_resize_cv_u8: cv2.resize(uint8 image, (Wd, Hd), interpolation=cv2.INTER_LANCZOS4 | cv2.INTER_AREA), the resampling of controlnet_aux's
+ *   resize_image (util.py:87-97: Lanczos4 when the picture is enlarged, area otherwise), src [M, Hs, Ws, 3] -> dst [M, Hd, Wd, 3].  The rules are
+ *   restated from OpenCV's published generic (non-SIMD) path; coefficient details have differed between OpenCV releases, and parity with the cv2
+ *   package is NOT pinned by a test here (tests/test_resize_cv.py pins them against an independent restatement and against their fp64
+ *   definitions).  `rule` names the arithmetic, the caller picks it as cv2 does (pcdms_amd/preprocess.py: resize_cv); xtab / ytab are the tables of
+ *   the two axes, int32 in DEVICE memory, built on the host.  Per axis scale = 1.0 / ((double)n_out / (double)n_in).
+ *   rule 0, INTER_LANCZOS4 (any size change; no antialiasing when reducing).  Table [s (n_out) | coeff (n_out * 8)].  For output d:
+ *     f = (float)((d + 0.5) * scale - 0.5), s = floor(f), t = f - s in fp32; the eight taps are the sources s - 3 .. s + 4, each clamped into
+ *     [0, n_in - 1].  Real coefficients for t >= FLT_EPSILON, in double: y0 = -(t + 3) pi / 4, s0 = sin(y0), c0 = cos(y0),
+ *     c_i = (float)((a_i s0 + b_i c0) / (y_i y_i)) with y_i = -(t + 3 - i) pi / 4 and (a_i, b_i) = (1, 0), (-r, -r), (0, 1), (r, -r), (-1, 0), (r, r),
+ *     (0, -1), (-r, r), r = 0.70710678118654752440; they are summed in fp32 in index order and each multiplied by 1.f / sum; for t < FLT_EPSILON
+ *     they are (0, 0, 0, 1, 0, 0, 0, 0).  coeff = rint(c_i * 2048) (ties to even) saturated to int16; the eight need not sum to 2048.
+ *     S = sum src alpha in int32 per source row, out = clip8((sum_k S_k beta_k + 2^21) >> 22), the vertical sum in 64-bit integers (so no image
+ *     overflows it; an int32 accumulator differs only where |sum| >= 2^31, which pictures do not reach).  Sines and cosines are taken on the host
+ *     only: the device reads integers.
+ *   rule 1, INTER_AREA on integer ratios (scale_x, scale_y integers >= 1 within DBL_EPSILON; no tables, NULL is fine): the sx x sy box of every
+ *     output; 2 x 2: (a + b + c + d + 2) >> 2; any other box: the int32 sum times (float)(1.f / (sx sy)) as ONE fp32 multiply, rounded to nearest
+ *     even and saturated.  -1 when a ratio is no such integer or sx sy > 2^23.
+ *   rule 2, INTER_AREA proper (scale_x >= 1 and scale_y >= 1, else -1).  Table [count (n_out) | source (n_out * k) | weight as fp32 bits
+ *     (n_out * k)], k = (int)scale + 2; output d lists, with f1 = d scale, f2 = f1 + scale, cell = min(scale, n_in - f1), s1 = ceil(f1),
+ *     s2 = min(floor(f2), n_in - 1), s1 = min(s1, s2): (s1 - 1, (float)((s1 - f1) / cell)) if s1 - f1 > 1e-3; (j, (float)(1.0 / cell)) for
+ *     j = s1 .. s2 - 1; (s2, (float)(min(min(f2 - s2, 1.0), cell) / cell)) if f2 - s2 > 1e-3.  fp32, every multiply and add its own IEEE operation
+ *     (no contraction, as pcdm_resize_cubic_f32): per source row of an output row, in table order, buf = 0 then buf = buf + (float)src alpha entry
+ *     by entry; sum = beta buf for the first row, sum = sum + beta buf for every later one; out = rint(sum) (ties to even), saturated.
+ *   rule 3, INTER_AREA when either axis enlarges (cv2 then takes its 8-bit bilinear path with other indices).  Table [s (n_out) | w0, w1
+ *     (n_out * 2)]: s = floor(d scale), t = (float)((d + 1) - (s + 1) (1 / scale)), t = 0 if t <= 0 else t - floor(t), on BOTH axes;
+ *     w0 = rint((1 - t) * 2048), w1 = rint(t * 2048); horizontally s >= n_in - 1 is clamped to n_in - 1 with t = 0.  The rows s, s + 1 and the
+ *     columns s, s + 1 are clamped into the image on the device and the arithmetic is pcdm_resize_linear_u8's: S = src[s] w0 + src[s + 1] w1,
+ *     out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Weights are clamped into [0, 2048].
+ *   Equal sizes copy under every rule (cv2's dsize == ssize return) and read no table.  Every table entry is clamped on the device -- indices
+ *   into the image, counts into [0, k], coefficients into their range -- so a wrong table gives wrong pixels, never an access outside src or
+ *   dst.  One launch, a lane per output pixel; no workspace, no atomics, no host synchronisation; reruns are bit-identical and an image's result
+ *   does not depend on its place in the batch.  Returns -1 and writes nothing for a NULL src or dst, non-positive sizes, M < 0, an unknown rule,
+ *   a NULL table the rule needs, or 2^31 bytes or more on either side; M = 0 returns 0. */
 int pcdm_pose_tables(int32_t* tables, int count);
 int64_t pcdm_pose_ws_bytes(int M, int P);
 int pcdm_pose_draw(const float* keypoints, const float* scores, int M, int P, int Hd, int Wd, int hands, int faces, const int32_t* tables, void* out,
                    void* ws, int64_t ws_bytes, pcdm_stream_t s);
 int pcdm_resize_linear_u8(const void* src, int M, int Hs, int Ws, void* dst, int Hd, int Wd, pcdm_stream_t s);
+int pcdm_resize_cv_u8(const void* src, int M, int Hs, int Ws, void* dst, int Hd, int Wd, int rule, const int32_t* xtab, const int32_t* ytab,
+                      pcdm_stream_t s);
 
 /* ---- The whole-body pose estimator: image + person boxes -> 133 keypoints and scores per box (what Wholebody.__call__ gets from its second
  * network, the top-down DWPose-l of mmpose: CSPNeXt-l backbone, RTMCC head, SimCC decoding).  The boxes come from the person detector below

@@ -19,8 +19,8 @@ from .encoders import CLIPVisionModelWithProjection, Dinov2Model  # noqa: F401,E
 from . import metrics  # noqa: F401,E402
 from .metrics import pick_best, psnr, ssim  # noqa: F401,E402
 from . import preprocess  # noqa: F401,E402
-from .preprocess import clip_pixel_values, resize, resize_cv_cubic, stage2_inputs, stage3_inputs  # noqa: F401,E402
+from .preprocess import clip_pixel_values, resize, resize_cv, resize_cv_cubic, stage2_inputs, stage3_inputs  # noqa: F401,E402
 from . import pose  # noqa: F401,E402
-from .pose import DWPoseEstimator, PersonDetector, detect_people, detect_size, draw_pose, estimate_pose_map, wholebody_to_openpose  # noqa: F401,E402
+from .pose import DWPoseEstimator, PersonDetector, detect_people, detect_size, draw_pose, estimate_pose_map, resize_image, wholebody_to_openpose  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -183,6 +183,7 @@ _SIGS = {
     "pcdm_pose_ws_bytes": ([_I, _I], _L),
     "pcdm_pose_draw": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
     "pcdm_resize_linear_u8": ([_P, _I, _I, _I, _P, _I, _I, _P], C.c_int),
+    "pcdm_resize_cv_u8": ([_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P], C.c_int),
     "pcdm_pose_crop": ([_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P], C.c_int),
     "pcdm_conv2d_f32_act": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P], C.c_int),
     "pcdm_dwconv5_silu_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P], C.c_int),

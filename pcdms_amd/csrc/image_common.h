@@ -1,4 +1,4 @@
-// What more than one of misc.hip / image_metrics.hip / image_prep.hip / eval_nets.hip / pose_draw.hip / pose_net.hip / detect.hip uses, and nothing else.  Internal linkage: each unit gets its own.
+// What more than one of misc.hip / image_metrics.hip / image_prep.hip / eval_nets.hip / pose_draw.hip / pose_net.hip / detect.hip / resize_cv.hip uses, and nothing else.  Internal linkage: each unit gets its own.
 #pragma once
 #include "pcdm_device.h"
 

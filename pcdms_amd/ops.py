@@ -1394,6 +1394,43 @@ def resize_linear_u8(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     return dst
 
 
+RESIZE_CV_LANCZOS4, RESIZE_CV_AREA_INT, RESIZE_CV_AREA, RESIZE_CV_AREA_LINEAR = 0, 1, 2, 3   # pcdm_resize_cv_u8's `rule`
+
+
+def resize_cv_table_ints(n_in: int, n_out: int, rule: int) -> int:
+    """int32 entries of one axis table of ``resize_cv_u8`` (include/pcdm.h: pcdm_resize_cv_u8); 0: the rule reads no table."""
+    if rule == RESIZE_CV_LANCZOS4:
+        return n_out * 9
+    if rule == RESIZE_CV_AREA_LINEAR:
+        return n_out * 3
+    if rule == RESIZE_CV_AREA:
+        return n_out * (1 + 2 * (int(1.0 / (float(n_out) / float(n_in))) + 2))
+    return 0
+
+
+def resize_cv_u8(src: torch.Tensor, dst: torch.Tensor, rule: int, xtab: Optional[torch.Tensor] = None, ytab: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src uint8 [M, Hs, Ws, 3] -> dst uint8 [M, Hd, Wd, 3]: OpenCV's 8-bit INTER_LANCZOS4 / INTER_AREA in the arithmetic ``rule`` names, by the int32
+    device tables of the two axes (None where the rule reads none: integer-ratio area, equal sizes); include/pcdm.h: pcdm_resize_cv_u8."""
+    _c(src, torch.uint8); _c(dst, torch.uint8)
+    assert src.dim() == 4 and dst.dim() == 4 and src.shape[0] == dst.shape[0] and src.shape[3] == 3 and dst.shape[3] == 3 and src.device == dst.device, \
+        (src.shape, dst.shape)
+    rule = int(rule)
+    if rule not in (RESIZE_CV_LANCZOS4, RESIZE_CV_AREA_INT, RESIZE_CV_AREA, RESIZE_CV_AREA_LINEAR):
+        raise ValueError(f"rule must be 0 .. 3: {rule}")
+    (Hs, Ws), (Hd, Wd) = (int(v) for v in src.shape[1:3]), (int(v) for v in dst.shape[1:3])
+    same = (Hs, Ws) == (Hd, Wd)
+    for t, n_in, n_out, what in ((xtab, Ws, Wd, "xtab"), (ytab, Hs, Hd, "ytab")):
+        need = 0 if same else resize_cv_table_ints(n_in, n_out, rule)
+        if need == 0:
+            assert t is None, f"{what}: rule {rule} reads no table for {n_in} -> {n_out}"
+        else:
+            assert t is not None and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == need and t.device == src.device, \
+                (what, None if t is None else (t.dtype, t.is_contiguous(), t.numel()), need)
+    call = lambda: _lib.lib().pcdm_resize_cv_u8(_ptr(src), src.shape[0], Hs, Ws, _ptr(dst), Hd, Wd, rule, _ptr(xtab), _ptr(ytab), _stream(src))  # noqa: E731
+    _chk(_launch(src, call, "resize_cv_u8", float(dst.numel()), (Hs, Ws, Hd, Wd, rule)), "pcdm_resize_cv_u8")
+    return dst
+
+
 # ------------------------------------------------------------------------------------ pose estimator (pcdms_amd/pose.py: DWPoseEstimator is the public surface)
 CONV_ACT_NONE, CONV_ACT_RELU, CONV_ACT_SILU = 0, 1, 2
 

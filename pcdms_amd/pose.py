@@ -9,8 +9,11 @@ The keypoints themselves come from ``DWPoseEstimator``: the reference's second n
 RTMCC head, SimCC decoding) in exact fp32 on the device, image + person boxes -> 133 keypoints and scores per box; ``estimate_pose_map`` chains
 it with the drawing.  The boxes come from ``PersonDetector``: the reference's first network (mmdet's YOLOX-l) with its label, score and NMS
 filters, image -> person boxes (``detect_people``; ``estimate_pose_map(..., detector=...)``).  Without a detector and without boxes the box is
-the whole image -- what the reference does when its detector finds nothing (dwpose/wholebody.py:78-79).  ``controlnet_aux.util.resize_image``
-(cv2 Lanczos / area resampling) is not restated: the detection frame is made with ``preprocess.resize``.  mmpose, mmdet and mmcv are not
+the whole image -- what the reference does when its detector finds nothing (dwpose/wholebody.py:78-79).  ``resize_image`` is
+``controlnet_aux.util.resize_image``, the frame both networks see: OpenCV's 8-bit Lanczos4 when the picture is enlarged, its area resampling
+otherwise (``preprocess.resize_cv``; restated from OpenCV's published generic path, coefficient details have differed between OpenCV releases and
+parity with the ``cv2`` package is not pinned by a test).  ``estimate_pose_map`` makes its frame with it under ``frame_resize="reference"``; the
+default, ``"pillow"``, keeps ``preprocess.resize`` (Pillow bicubic).  mmpose, mmdet and mmcv are not
 dependencies; both networks are restated from their published definitions (include/pcdm.h) and checked against fp64 restatements on synthetic
 weights (tests/test_dwpose.py, tests/test_person_detector.py), so parity with mmpose and mmdet on the published checkpoints is NOT pinned by a
 test that runs by default.
@@ -64,6 +67,17 @@ def detect_size(H: int, W: int, resolution: int) -> Tuple[int, int]:
     H *= k
     W *= k
     return int(round(H / 64.0)) * 64, int(round(W / 64.0)) * 64
+
+
+def resize_image(image_u8: torch.Tensor, resolution: int) -> torch.Tensor:
+    """``controlnet_aux.util.resize_image(image, resolution)`` on the device: uint8 ``[H, W, 3]`` (or ``[M, H, W, 3]``) -> the ``detect_size`` frame,
+    with ``cv2.INTER_LANCZOS4`` when ``k = resolution / min(H, W) > 1`` and ``cv2.INTER_AREA`` otherwise (``preprocess.resize_cv``)."""
+    if image_u8.dim() not in (3, 4) or image_u8.shape[-1] != 3 or image_u8.dtype != torch.uint8:
+        raise ValueError(f"an image is uint8 [H, W, 3] or [M, H, W, 3]: got {image_u8.dtype} {tuple(image_u8.shape)}")
+    H, W = int(image_u8.shape[-3]), int(image_u8.shape[-2])
+    Hd, Wd = detect_size(H, W, resolution)
+    k = float(resolution) / min(float(H), float(W))
+    return preprocess.resize_cv(image_u8, (Wd, Hd), "lanczos4" if k > 1 else "area")
 
 
 def _tables(device: torch.device) -> torch.Tensor:
@@ -719,19 +733,22 @@ def detect_people(detector: PersonDetector, images_u8: torch.Tensor) -> Tuple[to
 
 def estimate_pose_map(estimator: DWPoseEstimator, image_u8: torch.Tensor, *, detect_resolution: int = 512, image_resolution: int = 512,
                       boxes=None, hands: bool = True, faces: bool = False, return_keypoints: bool = False,
-                      detector: Optional[PersonDetector] = None):
+                      detector: Optional[PersonDetector] = None, frame_resize: str = "pillow"):
     """``DWposeDetector.__call__(image, detect_resolution, image_resolution)``: uint8 RGB ``[H, W, 3]`` on the device -> the pose map uint8
     ``[H', W', 3]``, (H', W') = ``detect_size(H, W, image_resolution)``.  The image is resized to the detection frame
-    ``detect_size(H, W, detect_resolution)`` with ``preprocess.resize`` (Pillow bicubic; the reference's cv2 Lanczos / area resampling is not
-    restated), the estimator runs on ``boxes`` (pixels of the detection frame), and every box's person is drawn.  ``boxes`` None: with a
+    ``detect_size(H, W, detect_resolution)`` -- ``frame_resize="pillow"`` (the default): with ``preprocess.resize`` (Pillow bicubic);
+    ``"reference"``: with ``resize_image``, the reference's cv2 Lanczos4 / area resampling -- the estimator runs on ``boxes`` (pixels of the
+    detection frame), and every box's person is drawn.  ``boxes`` None: with a
     ``detector`` they are ``detect_people(detector, frame)`` -- the reference's whole pipeline, pixels -> boxes -> keypoints -> map; without one
     the box is the whole frame, what the reference does when its detector finds nothing.
     ``return_keypoints``: ``(map, keypoints [R, 133, 2], scores [R, 133], (Hd, Wd))`` -- what tools/extract_pose.py writes next to the image."""
     if image_u8.dim() != 3 or image_u8.dtype != torch.uint8 or image_u8.shape[2] != 3:
         raise ValueError(f"an image is uint8 [H, W, 3]: got {image_u8.dtype} {tuple(image_u8.shape)}")
+    if frame_resize not in ("pillow", "reference"):
+        raise ValueError(f"frame_resize must be 'pillow' or 'reference', not {frame_resize!r}")
     H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
     Hd, Wd = detect_size(H, W, detect_resolution)
-    frame = preprocess.resize(image_u8, (Wd, Hd))
+    frame = preprocess.resize(image_u8, (Wd, Hd)) if frame_resize == "pillow" else resize_image(image_u8, detect_resolution)
     if boxes is None and detector is not None:
         boxes, _ = detect_people(detector, frame)
     kp, sc = estimator(frame, boxes)

@@ -17,6 +17,7 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -200,3 +201,151 @@ def resize_cv_cubic(image: torch.Tensor, size: Sequence[int], *, divisor: Option
     if not 0 <= int(index) < out.shape[0]:
         raise ValueError(f"index {index} outside the batch of {out.shape[0]}")
     return ops.resize_cubic_f32(image.contiguous(), out, int(index), nchw=layout == "nchw", divisor=0.0 if divisor is None else float(divisor))
+
+
+# ------------------------------------------------------------------------------------------------ cv2.resize(uint8, INTER_LANCZOS4 | INTER_AREA)
+_F32 = np.float32
+_FLT_EPSILON, _DBL_EPSILON = float(np.finfo(np.float32).eps), float(np.finfo(np.float64).eps)
+_COEF_SCALE = 2048                           # OpenCV: INTER_RESIZE_COEF_SCALE = 1 << 11
+_S45 = 0.70710678118654752440
+_LANCZOS_CS = ((1.0, 0.0), (-_S45, -_S45), (0.0, 1.0), (_S45, -_S45), (-1.0, 0.0), (_S45, _S45), (0.0, -1.0), (-_S45, _S45))
+
+
+def cv_scale(n_in: int, n_out: int) -> float:
+    """OpenCV's per-axis scale: ``1.0 / ((double)n_out / (double)n_in)``."""
+    return 1.0 / (float(n_out) / float(n_in))
+
+
+def cv_lanczos4_coeffs(t) -> list:
+    """The eight fp32 Lanczos4 coefficients of the fraction ``t`` (fp32), OpenCV's ``interpolateLanczos4`` (include/pcdm.h: rule 0)."""
+    t = _F32(t)
+    if t < _F32(_FLT_EPSILON):
+        return [_F32(v) for v in (0, 0, 0, 1, 0, 0, 0, 0)]
+    y0 = -(float(t) + 3.0) * math.pi / 4
+    s0, c0 = math.sin(y0), math.cos(y0)
+    c, total = [], _F32(0)
+    for i, (a, b) in enumerate(_LANCZOS_CS):
+        y = -(float(t) + 3.0 - i) * math.pi / 4
+        c.append(_F32((a * s0 + b * c0) / (y * y)))
+        total = _F32(total + c[-1])
+    inv = _F32(_F32(1) / total)
+    return [_F32(v * inv) for v in c]
+
+
+def _cv_fixed(v) -> int:
+    """``saturate_cast<short>(v * INTER_RESIZE_COEF_SCALE)``: one fp32 product, rounded to nearest even"""
+    return int(min(max(np.rint(_F32(_F32(v) * _F32(_COEF_SCALE))), -32768), 32767))
+
+
+def cv_lanczos4_table(n_in: int, n_out: int) -> list:
+    """``[s (n_out) | coeff (n_out * 8)]`` of one axis (include/pcdm.h: pcdm_resize_cv_u8, rule 0)."""
+    scale = cv_scale(n_in, n_out)
+    ofs, coeff = [], []
+    for d in range(n_out):
+        f = _F32((d + 0.5) * scale - 0.5)
+        s = math.floor(float(f))
+        ofs.append(int(s))
+        coeff += [_cv_fixed(c) for c in cv_lanczos4_coeffs(_F32(f - _F32(s)))]
+    return ofs + coeff
+
+
+def cv_area_table(n_in: int, n_out: int) -> list:
+    """``[count (n_out) | source (n_out * k) | weight bits (n_out * k)]`` of one axis, ``k = int(scale) + 2``: OpenCV's ``computeResizeAreaTab``
+    regrouped per output (include/pcdm.h: rule 2)."""
+    scale = cv_scale(n_in, n_out)
+    k = int(scale) + 2
+    count, src, w = [], [0] * (n_out * k), [_F32(0)] * (n_out * k)
+    for d in range(n_out):
+        f1 = d * scale
+        f2 = f1 + scale
+        cell = min(scale, n_in - f1)
+        s1, s2 = math.ceil(f1), min(math.floor(f2), n_in - 1)
+        s1 = min(s1, s2)
+        ent = []
+        if s1 - f1 > 1e-3:
+            ent.append((s1 - 1, _F32((s1 - f1) / cell)))
+        ent += [(j, _F32(1.0 / cell)) for j in range(s1, s2)]
+        if f2 - s2 > 1e-3:
+            ent.append((s2, _F32(min(min(f2 - s2, 1.0), cell) / cell)))
+        assert len(ent) <= k, (n_in, n_out, d, len(ent), k)
+        count.append(len(ent))
+        for j, (si, a) in enumerate(ent):
+            src[d * k + j], w[d * k + j] = int(si), a
+    return count + src + np.asarray(w, dtype=np.float32).view(np.int32).tolist()
+
+
+def cv_area_linear_table(n_in: int, n_out: int, clamp_frac: bool) -> list:
+    """``[s (n_out) | w0, w1 (n_out * 2)]`` of one axis: the bilinear form INTER_AREA takes when an axis enlarges (include/pcdm.h: rule 3);
+    ``clamp_frac``: the x axis, where an index at the last column loses its fraction."""
+    scale = cv_scale(n_in, n_out)
+    inv = 1.0 / scale
+    ofs, coeff = [], []
+    for d in range(n_out):
+        s = math.floor(d * scale)
+        t = _F32((d + 1) - (s + 1) * inv)
+        t = _F32(0) if t <= 0 else _F32(t - np.floor(t))
+        if clamp_frac and s >= n_in - 1:
+            s, t = n_in - 1, _F32(0)
+        ofs.append(int(s))
+        coeff += [_cv_fixed(_F32(_F32(1) - t)), _cv_fixed(t)]
+    return ofs + coeff
+
+
+_CV_TABLES: Dict[tuple, torch.Tensor] = {}
+
+
+def _cv_table(n_in: int, n_out: int, rule: int, is_x: bool, device: torch.device) -> torch.Tensor:
+    key = (n_in, n_out, rule, is_x and rule == ops.RESIZE_CV_AREA_LINEAR, str(device))
+    if key not in _CV_TABLES:
+        if rule == ops.RESIZE_CV_LANCZOS4:
+            tab = cv_lanczos4_table(n_in, n_out)
+        elif rule == ops.RESIZE_CV_AREA:
+            tab = cv_area_table(n_in, n_out)
+        else:
+            tab = cv_area_linear_table(n_in, n_out, is_x)
+        t = torch.empty(len(tab), dtype=torch.int32, device=device)
+        t.copy_(torch.tensor(tab, dtype=torch.int32))
+        _CV_TABLES[key] = t
+    return _CV_TABLES[key]
+
+
+def cv_area_rule(Hs: int, Ws: int, Hd: int, Wd: int) -> int:
+    """The arithmetic ``cv2.resize(..., INTER_AREA)`` takes for these sizes: the integer-ratio box, true area, or -- when either axis enlarges --
+    its bilinear emulation."""
+    sx, sy = cv_scale(Ws, Wd), cv_scale(Hs, Hd)
+    if sx >= 1.0 and sy >= 1.0:
+        if abs(sx - round(sx)) < _DBL_EPSILON and abs(sy - round(sy)) < _DBL_EPSILON:
+            return ops.RESIZE_CV_AREA_INT
+        return ops.RESIZE_CV_AREA
+    return ops.RESIZE_CV_AREA_LINEAR
+
+
+def resize_cv(image_u8: torch.Tensor, size: Sequence[int], interpolation: str = "lanczos4") -> torch.Tensor:
+    """``cv2.resize(image, size, interpolation=cv2.INTER_LANCZOS4 | cv2.INTER_AREA)`` on the device: uint8 ``[H, W, 3]`` or ``[M, H, W, 3]`` ->
+    the same rank at ``size`` = ``(width, height)``.  ``"lanczos4"``: eight taps per axis in OpenCV's 8-bit fixed point, no antialiasing when
+    reducing.  ``"area"``: what OpenCV picks for the sizes -- the integer box (2 x 2 in integers, otherwise one fp32 multiply), true area in fp32,
+    or the 8-bit bilinear form when either axis enlarges.  Equal sizes copy.
+
+    OpenCV is not a dependency: the rules are restated from its published generic path (include/pcdm.h: pcdm_resize_cv_u8) and checked against an
+    independent restatement and their fp64 definitions (tests/test_resize_cv.py); coefficient details have differed between OpenCV releases, so
+    parity with the ``cv2`` package itself is NOT pinned by a test here -- the same standing as ``resize_cv_cubic``.  The per-axis tables are built
+    here on the host (the sines and cosines of Lanczos4 are never taken on the device), cached per ``(in, out, rule, device)`` and uploaded once;
+    after that one launch, no host synchronisation."""
+    if interpolation not in ("lanczos4", "area"):
+        raise ValueError(f"interpolation must be 'lanczos4' or 'area', not {interpolation!r}")
+    if image_u8.dim() not in (3, 4) or image_u8.shape[-1] != 3 or image_u8.dtype != torch.uint8:
+        raise ValueError(f"an image is uint8 [H, W, 3] or [M, H, W, 3]: got {image_u8.dtype} {tuple(image_u8.shape)}")
+    Wd, Hd = int(size[0]), int(size[1])
+    if Wd <= 0 or Hd <= 0:
+        raise ValueError(f"size must be positive: {tuple(size)}")
+    src = (image_u8 if image_u8.dim() == 4 else image_u8.unsqueeze(0)).contiguous()
+    M, Hs, Ws = (int(v) for v in src.shape[:3])
+    if Hs <= 0 or Ws <= 0:
+        raise ValueError(f"empty image: {tuple(image_u8.shape)}")
+    rule = ops.RESIZE_CV_LANCZOS4 if interpolation == "lanczos4" else cv_area_rule(Hs, Ws, Hd, Wd)
+    xtab = ytab = None
+    if (Hs, Ws) != (Hd, Wd) and rule != ops.RESIZE_CV_AREA_INT:
+        xtab, ytab = _cv_table(Ws, Wd, rule, True, src.device), _cv_table(Hs, Hd, rule, False, src.device)
+    out = torch.empty((M, Hd, Wd, 3), dtype=torch.uint8, device=src.device)
+    ops.resize_cv_u8(src, out, rule, xtab, ytab)
+    return out if image_u8.dim() == 4 else out[0]

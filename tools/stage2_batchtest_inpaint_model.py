@@ -13,7 +13,8 @@ With ``--pose_source keypoints`` the pose maps are not read as images: ``<pose n
 the pose image would be is rendered on the device by ``pcdms_amd.pose.draw_pose`` -- the pixels tools/render_pose.py writes for that file.
 With ``--pose_source estimator --pose_weights CKPT`` no pose file is read at all: the pose map of each source / target IMAGE is estimated on the
 device by ``pcdms_amd.pose.estimate_pose_map`` (DWPose-l from the mmpose checkpoint CKPT; the whole image is the person box: tools/README.md --
-or, with ``--pose_det_weights CKPT``, the boxes of the person detector, YOLOX-l from the mmdet checkpoint, as in the reference).
+or, with ``--pose_det_weights CKPT``, the boxes of the person detector, YOLOX-l from the mmdet checkpoint, as in the reference;
+``--pose_frame_resize reference`` makes the detection frame with the reference's ``resize_image`` instead of Pillow bicubic).
 That map is estimated from the picture as it lies on disk with detect_resolution = image_resolution = 512 and then resized to the driver's size
 like a pose file; it is NOT the file tools/extract_pose.py writes, which follows the reference's ``single_extract_pose.py`` (the picture resized to
 1024 x 1024 first, image_resolution 1024).  A pair's maps are estimated again where the driver reads a pose file again (the grid's thumbnails).
@@ -88,13 +89,15 @@ def load_detector(args):
                                             num_classes=getattr(args, "pose_det_num_classes", 80))
 
 
-def load_pose(path: str, source: str, device, on_device: bool, image_path: str = None, estimator=None, detector=None):
+def load_pose(path: str, source: str, device, on_device: bool, image_path: str = None, estimator=None, detector=None, frame_resize: str = "pillow"):
     """The pose map the driver reads at ``path``, not yet resized: decoded from the image file (``source`` "image"), rendered on ``device`` from
     the keypoint file of the same name with the extension .npz ("keypoints"), or estimated on ``device`` from the picture at ``image_path`` by
-    ``estimator`` ("estimator"; with ``detector`` the person boxes come from it, else the box is the whole picture).  A uint8 [h, w, 3] tensor on
+    ``estimator`` ("estimator"; with ``detector`` the person boxes come from it, else the box is the whole picture; ``frame_resize``: how the
+    detection frame is made, ``--pose_frame_resize``).  A uint8 [h, w, 3] tensor on
     ``device`` (``on_device``) or a PIL image."""
     if source == "estimator":
-        pose = P.estimate_pose_map(estimator, torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).to(device), detector=detector)
+        pose = P.estimate_pose_map(estimator, torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).to(device), detector=detector,
+                                   frame_resize=frame_resize)
         return pose if on_device else Image.fromarray(pose.cpu().numpy())
     if source == "keypoints":
         with np.load(os.path.splitext(path)[0] + ".npz") as f:
@@ -187,7 +190,8 @@ def inference(args, rank, select_test_datas):
         t_pose_path = args.pose_path + data["target_image"].replace(".jpg", "_pose.jpg")
         t_img_dev = None
         load = lambda p: Image.open(p).convert("RGB").resize((W, H), Image.BICUBIC)  # noqa: E731
-        pose_of = lambda p, img, dev: load_pose(p, pose_source, device, dev, img, estimator, detector)  # noqa: E731
+        pose_of = lambda p, img, dev: load_pose(p, pose_source, device, dev, img, estimator, detector,  # noqa: E731
+                                                getattr(args, "pose_frame_resize", "pillow"))
         load_p = lambda p, img: pose_of(p, img, False).resize((W, H), Image.BICUBIC)  # noqa: E731
         if pre_gpu:      # decode on the host, upload the raw pixels once per image, everything else on the device (pcdms_amd/preprocess.py)
             raw = lambda p: torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device)  # noqa: E731
@@ -292,6 +296,8 @@ def build_parser():
     p.add_argument("--pose_input_size", type=int, nargs=2, default=(288, 384), metavar=("W", "H"), help="crop size of the --pose_weights network")
     p.add_argument("--pose_widen_factor", type=float, default=1.0, help="CSPNeXt widen_factor of --pose_weights (DWPose-l: 1)")
     p.add_argument("--pose_deepen_factor", type=float, default=1.0, help="CSPNeXt deepen_factor of --pose_weights (DWPose-l: 1)")
+    p.add_argument("--pose_frame_resize", choices=("pillow", "reference"), default="pillow",
+                   help="--pose_source estimator: the detection frame by Pillow bicubic (default) or by the reference's resize_image (cv2 Lanczos4 / area)")
     p.add_argument("--pose_det_weights", type=str, default=None,
                    help="the mmdet YOLOX-l checkpoint for --pose_source estimator: person boxes from the detector (default: the whole picture)")
     p.add_argument("--pose_det_size", type=int, default=640, help="square input size of the --pose_det_weights network (YOLOX-l: 640)")
