@@ -5,6 +5,7 @@ classes whose weights live as packed bf16 device buffers rather than ``nn.Parame
 Plus the three things every ``from_pretrained`` does: read ``config.json``, read the checkpoint file, PyTorch-default fresh init."""
 from __future__ import annotations
 
+import itertools
 import json
 import math
 from pathlib import Path
@@ -15,6 +16,14 @@ import torch
 
 from . import _lib
 from .ops import BF16
+
+#: process-wide serial numbers of model and context objects.  A long-lived caller (a pipeline's captured graph) that has to tell "the same
+#: model" from "another model" compares these, never ``id()``: CPython hands the address of a dropped object to the next one built.
+_SERIAL = itertools.count(1)
+
+
+def next_serial() -> int:
+    return next(_SERIAL)
 
 
 class Config(SimpleNamespace):
@@ -77,6 +86,7 @@ class HipModel:
     _reshape_same_numel = False   # load_state_dict: accept a tensor of another shape with the expected number of elements (reshaped)
 
     def __init__(self):
+        self._serial = next_serial()
         self._device = torch.device("cpu")
         self._dtype = torch.float32                              # I/O dtype only; arithmetic is bf16 x bf16 -> fp32 on MFMA
         self._sd: Optional[Dict[str, torch.Tensor]] = None       # fp32 CPU master copy (the checkpoint's key names)

@@ -306,7 +306,7 @@ class Stage2_InpaintDiffusionPipeline:
         else:
             x_in = ops.assemble_input(st["lat"], st["rep"], st["mask"], st["masked"], st["x_in"])
         if st.get("ctx") is not None:
-            eps = st["ctx"].forward(x_in, st["timesteps"], st["step"], B, h, w, st["pose_b"], out=st["eps_c"])
+            eps = st["ctx"].forward(x_in, st["timesteps"], st["step"], B, h, w, st["pose_b"], out=st["eps_c"], L=st["L"])
         else:
             eps = unet._forward_nhwc(x_in, B, h, w, st["timesteps"], st["cond"], step_dev=st["step"])
         cfg, g, e = st["rep"] == 2, st["g"], eps
@@ -324,6 +324,17 @@ class Stage2_InpaintDiffusionPipeline:
         else:
             ops.cfg_step(e, cfg, g, st["lat"], st["lat"], st["coef"], st["step"])
         ops.advance_step(st["step"])
+
+    @staticmethod
+    def _weights_generation(unet, dev):
+        """What a captured step's weight and workspace pointers depend on: which model (its process-wide serial number), which packing
+        of its weights, which split-K workspace."""
+        return (unet._serial, getattr(unet, "_pack_gen", 0), ops.workspace_generation(dev))
+
+    @staticmethod
+    def _context_generation(ctx, w_gen):
+        """What the one-off tuning step of the C schedule was made for: which context (its serial number), which weights and workspace."""
+        return (ctx._serial, w_gen)
 
     @staticmethod
     def _zero_history(st):
@@ -354,7 +365,8 @@ class Stage2_InpaintDiffusionPipeline:
         kind = "unipc" if unipc else ("dpm_sde" if sde else "dpm") if dpm else ("ms", sde, scaled) if ms else "linear"
         tdt = torch.float32 if timesteps.dtype.is_floating_point else torch.int64   # the scheduler's own: float32 tables keep fractional timesteps
         key = (B, h, w, n, rep, n0, tuple(feature_f.shape), None if mask is None else tuple(mask.shape), tuple(masked.shape),
-               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, kind, bool(shared_halves), tdt)
+               None if pose_cond is None else tuple(pose_cond.shape), prior_embed is None, kind, bool(shared_halves), tdt,
+               bool(self.c_schedule))   # (the captured step calls either the Python schedule or the C context: each refreshes its own buffers)
         st = self._st if self._graph_key == key else {}
         if not st:
             st.update(B=B, h=h, w=w, rep=rep, unipc=unipc, dpm=dpm, ms=ms, scaled=scaled, noise=None,
@@ -400,8 +412,9 @@ class Stage2_InpaintDiffusionPipeline:
         if st.get("freeu", freeu) != freeu:
             self._graph = None
         st["freeu"] = freeu
-        # pipe.unet replaced, weights re-packed (load_state_dict / .to), or a split-K workspace re-allocated: re-capture
-        w_gen = (id(unet), getattr(unet, "_pack_gen", 0), ops.workspace_generation(dev))
+        # pipe.unet replaced, weights re-packed (load_state_dict / .to), or a split-K workspace re-allocated: re-capture.  The model is named
+        # by its serial number, never by id(): a model built after the old one was dropped may sit at the same address
+        w_gen = self._weights_generation(unet, dev)
         if st.get("w_gen") != w_gen:
             self._graph = None
         st["ctx"] = None
@@ -413,7 +426,7 @@ class Stage2_InpaintDiffusionPipeline:
             # one Python-schedule step first, once per (context, weights, workspace): it tunes every GEMM shape of this batch size.  The
             # device step counter is reset BEFORE it (a reused `st` still holds the last run's count, one past the end of the
             # timestep / coefficient tables: ADVICE r3)
-            if st.get("c_tuned") != (id(self._ctx), w_gen) and dev.type == "cuda":
+            if st.get("c_tuned") != self._context_generation(self._ctx, w_gen) and dev.type == "cuda":
                 lat0 = lat.clone()
                 st["step"].zero_()
                 self._zero_history(st)
@@ -424,14 +437,15 @@ class Stage2_InpaintDiffusionPipeline:
                 self._ctx.sync_tiles()
                 # the eager step may have grown the split-K workspace (-> a new workspace generation): store the generation AFTER it, or
                 # the next call would tune a second time
-                w_gen2 = (id(unet), getattr(unet, "_pack_gen", 0), ops.workspace_generation(dev))
+                w_gen2 = self._weights_generation(unet, dev)
                 if w_gen2 != w_gen:
                     self._graph = None        # (a graph captured on the old workspace addresses must not be replayed)
                 w_gen = w_gen2
-                st["c_tuned"] = (id(self._ctx), w_gen)
+                st["c_tuned"] = self._context_generation(self._ctx, w_gen)
             st["pose_b"] = self._ctx.prepare_conditioning(B, h, w, feature_f, prior_embed, pose_cond, zero_ctx_batches=n0,
                                                           shared_cfg_input=st["cond"].shared_halves)
-            self._ctx.prepare_timesteps(st["timesteps"], B, h, w)
+            self._ctx.prepare_timesteps(st["timesteps"], B, h, w, L=feature_f.shape[1])
+            st["L"] = feature_f.shape[1]   # (in `key` through feature_f.shape: the captured forward's context length)
             st["eps_c"] = st.get("eps_c") if st.get("eps_c") is not None and st["eps_c"].shape[0] == B else \
                 torch.empty(B, unet.config.out_channels, h, w, dtype=torch.float32, device=dev)
             st["ctx"] = self._ctx
@@ -456,7 +470,7 @@ class Stage2_InpaintDiffusionPipeline:
                 self._zero_history(st)
                 self._graph = graph
                 st["g_captured"] = g
-                w_gen = (id(unet), getattr(unet, "_pack_gen", 0), ops.workspace_generation(dev))   # (the warm-up may have grown it)
+                w_gen = self._weights_generation(unet, dev)   # (the warm-up may have grown it)
             st["w_gen"] = w_gen
             for i in range(n):
                 self._graph.replay()
@@ -469,9 +483,18 @@ class Stage2_InpaintDiffusionPipeline:
                 if callback is not None and i % callback_steps == 0:
                     callback(i, timesteps[i], st["lat"])
         out = st["lat"].clone()
-        # the device step counter indexes the per-call time table inside the kernels: they bound it (a counter beyond the table is clamped,
-        # never an out-of-bounds read) and raise a flag -- read once per sampling call (one 4-byte copy behind the loop)
-        if (hasattr(unet, "step_overflow") and unet.step_overflow()) or (ms and int(st["step_err"].item()) != 0):
+        # the device step counter indexes the per-call time table inside the UNet's kernels: they bound it (a counter beyond the table is
+        # clamped, never an out-of-bounds read of THAT table) and raise a flag -- read once per sampling call (one 4-byte copy behind the
+        # loop).  The table-step samplers' kernels clamp and report likewise (st["step_err"]); pcdm_cfg_step / pcdm_unipc_step /
+        # pcdm_dpmpp_step do NOT bound their coefficient row, so by the time this error is raised on DDIM, UniPC or DPM-Solver++ a step has
+        # read past st["coef"].  The flag lives where
+        # the schedule that ran keeps it: in the context's workspace on the C schedule (no kernel of such a call writes the Python
+        # schedule's), in the UNet's scratch otherwise -- one 4-byte read per call either way, no second synchronisation
+        if st["ctx"] is not None:
+            overflow = st["ctx"].step_overflow(B, h, w, L=feature_f.shape[1])
+        else:
+            overflow = hasattr(unet, "step_overflow") and unet.step_overflow()
+        if overflow or (ms and int(st["step_err"].item()) != 0):
             raise RuntimeError("the device step counter left the time-embedding table of this sampling call (clamped on the device): "
                                "the schedule ran more steps than prepare_conditioning(timesteps=...) was given")
         return out

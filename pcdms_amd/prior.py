@@ -312,13 +312,19 @@ class Stage1_PriorPipeline:
             raise ValueError(f"Unexpected latents shape, got {latents.shape}, expected {shape}")
         return (latents.to(device, torch.float32) * scheduler.init_noise_sigma).contiguous()
 
+    @staticmethod
+    def _prior_generation(prior):
+        """Which prior and which packing of its weights a captured step points into.  The prior by its serial number, not id(): a prior built
+        after the old one was dropped may sit at the same address."""
+        return (prior._serial, getattr(prior, "_pack_gen", 0))
+
     def _run_graph(self, x, emb, sp, tp, ts, rows, noises, cfg_on, g):
         """The denoise loop (ref :453-483) as ONE captured step replayed ``len(ts)`` times: prior forward (timestep from a device
         table at the device step counter) -> ``pcdm_unclip_step_dev`` (CFG + scheduler step, coefficients and noise from device
         tables) -> ``pcdm_advance_step``.  ~150 launches of a few microseconds each per step otherwise pay the host's launch rate."""
         dev, prior = x.device, self.prior
         n = len(ts)
-        key = (tuple(x.shape), tuple(emb.shape), n, cfg_on, g, id(prior), getattr(prior, "_pack_gen", 0))
+        key = (tuple(x.shape), tuple(emb.shape), n, cfg_on, g) + self._prior_generation(prior)
         st = getattr(self, "_gst", None)
         if st is None or st["key"] != key:
             st = dict(key=key, x=torch.empty_like(x), emb=torch.empty_like(emb), sp=torch.empty_like(sp), tp=torch.empty_like(tp),

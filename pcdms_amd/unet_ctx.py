@@ -14,6 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib, ops
+from ._module import next_serial
 from .unet import Stage2_InapintUNet2DConditionModel, _resnets, _transformers
 
 
@@ -23,6 +24,7 @@ class UNetContext:
             unet._pack()
         self.unet = unet
         self._pack_gen = unet._pack_gen
+        self._serial = next_serial()   # process-wide: names this context in a caller's cache keys (id() can be that of a dropped context)
         lib = _lib.lib()
         cfg = _lib.UNetConfig()
         c = unet.config
@@ -46,6 +48,7 @@ class UNetContext:
             self._chk(lib.pcdm_unet_set_freeu(self._h, 1, *self._freeu), "pcdm_unet_set_freeu")
         self._keep = []       # tensors the context points into
         self._ws = {}
+        self._L = {}          # (B, h, w) -> the context length prepare_conditioning last ran with: the default of the calls that follow it
         self._register()
         self.sync_tiles()
 
@@ -154,44 +157,57 @@ class UNetContext:
                                                             ops._ptr(pose), pose_b, int(zero_ctx_batches),
                                                             ops._ptr(ws), ops._stream(ws)), "pcdm_unet_prepare_conditioning")
         self._chk(_lib.lib().pcdm_unet_set_shared_cfg_input(self._h, ops._ptr(ws), int(bool(shared_cfg_input))), "pcdm_unet_set_shared_cfg_input")
-        self._L = L
+        self._L[B, h, w] = L
         return pose_b
 
+    def _len(self, B: int, h: int, w: int, L: Optional[int]) -> int:
+        """The context length that selects the workspace of a call: the caller's, else the one ``prepare_conditioning`` last ran with at this
+        (B, h, w).  One context serves several lengths side by side; each has its own workspace, conditioning, time table and overflow flag."""
+        if L is not None:
+            return int(L)
+        if (B, h, w) not in self._L:
+            raise RuntimeError(f"prepare_conditioning has not run for B={B}, h={h}, w={w}")
+        return self._L[B, h, w]
+
     @torch.no_grad()
-    def prepare_timesteps(self, t_dev: torch.Tensor, B: int, h: int, w: int) -> None:
+    def prepare_timesteps(self, t_dev: torch.Tensor, B: int, h: int, w: int, L: Optional[int] = None) -> None:
         """After ``prepare_conditioning``: the time / class embeddings and every ``time_emb_proj`` for ALL steps of the device timestep table
         ``t_dev`` (``pcdm_unet_prepare_timesteps``); ``forward`` calls that pass the same ``t_dev`` with a step counter then launch nothing for them."""
         assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and t_dev.device == self.unet.device
         n = t_dev.numel()
         fn = _lib.lib().pcdm_unet_prepare_timesteps if t_dev.dtype == torch.int64 else _lib.lib().pcdm_unet_prepare_timesteps_f32
         nbytes = _lib.lib().pcdm_unet_time_table_bytes(self._h, n, B)
-        key = ("ttab", n, B)
+        L = self._len(B, h, w, L)
+        # one table per workspace and step count: it is filled from THAT workspace's class embedding and the workspace keeps its address, so
+        # two workspaces (another L, another h x w) must not share one, or the later prepare would rewrite the table the earlier one reads
+        key = ("ttab", B, h, w, L, n)
         tab = self._ws.get(key)
         if tab is None:
             tab = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.unet.device)
-        ws = self.workspace(B, h, w, self._L)
+        ws = self.workspace(B, h, w, L)
         self._chk(fn(self._h, ops._ptr(t_dev), n, ops._ptr(tab), ops._ptr(ws), ops._stream(ws)), "pcdm_unet_prepare_timesteps")
 
-    def step_overflow(self, B: int, h: int, w: int) -> bool:
+    def step_overflow(self, B: int, h: int, w: int, L: Optional[int] = None) -> bool:
         """``pcdm_unet_step_overflow``: did a forward on this shape's workspace find the device step counter outside the prepared time table?
         (clamped on the device, never an out-of-bounds read).  Synchronises."""
-        import ctypes as C
-        ws = self.workspace(B, h, w, self._L)
+        ws = self.workspace(B, h, w, self._len(B, h, w, L))
         flag = C.c_int(0)
         self._chk(_lib.lib().pcdm_unet_step_overflow(self._h, ops._ptr(ws), C.byref(flag), ops._stream(ws)), "pcdm_unet_step_overflow")
         return bool(flag.value)
 
     @torch.no_grad()
     def forward(self, x_in: torch.Tensor, t_dev: torch.Tensor, step_dev: Optional[torch.Tensor], B: int, h: int, w: int, pose_b: int,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_in NHWC bf16 [B, h, w, conv_in.cin]; t_dev int64 or float32 device tensor; returns fp32 NCHW eps."""
+                out: Optional[torch.Tensor] = None, L: Optional[int] = None) -> torch.Tensor:
+        """x_in NHWC bf16 [B, h, w, conv_in.cin]; t_dev int64 or float32 device tensor; returns fp32 NCHW eps.  ``L``: the context length whose
+        prepared workspace to run on (default: the one last prepared at this B, h, w)."""
         assert x_in.dtype == ops.BF16 and x_in.is_contiguous() and t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous()
         fn = _lib.lib().pcdm_unet_forward if t_dev.dtype == torch.int64 else _lib.lib().pcdm_unet_forward_f32
         if self._pack_gen != self.unet._pack_gen:
             raise RuntimeError("the UNet's weights were re-packed: build a new UNetContext")
-        ws = self.workspace(B, h, w, self._L)
+        L = self._len(B, h, w, L)
+        ws = self.workspace(B, h, w, L)
         if out is None:
             out = torch.empty(B, self.unet.config.out_channels, h, w, dtype=torch.float32, device=x_in.device)
         self._chk(fn(self._h, ops._ptr(x_in), ops._ptr(t_dev), ops._ptr(step_dev),
-                     B, h, w, self._L, pose_b, ops._ptr(ws), ops._ptr(out), ops._stream(x_in)), "pcdm_unet_forward")
+                     B, h, w, L, pose_b, ops._ptr(ws), ops._ptr(out), ops._stream(x_in)), "pcdm_unet_forward")
         return out
