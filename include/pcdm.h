@@ -22,7 +22,7 @@ extern "C" {
 
 typedef void* pcdm_stream_t; /* hipStream_t */
 
-#define PCDM_ABI_VERSION 5   /* what pcdm_version() returns for the library this header belongs to */
+#define PCDM_ABI_VERSION 6   /* what pcdm_version() returns for the library this header belongs to */
 int pcdm_version(void);
 /* 1 only for the test-only CPU lane emulator build (tests/emu); the product .so returns 0. */
 int pcdm_is_emulator(void);
@@ -50,6 +50,9 @@ int pcdm_groupnorm(const void* x1, int C1, const void* x2, int C2, int B, int HW
  * pre_out [M, N] bf16 must always be provided; it is WRITTEN (the reduced pre-norm tensor, for the residual / skip connections
  * that read it later) iff store_pre != 0 -- except on the two-launch path of very large slabs, which writes it regardless. */
 typedef struct pcdm_gn_splitk_src {
+    uint32_t struct_size;  /* = sizeof(pcdm_gn_splitk_src) of the header the HOST was compiled against (ABI 6), as pcdm_gemm_params.struct_size: zero-initialise
+                              the struct, set this; pcdm_groupnorm_splitk returns -1 for any other size before it reads another field -- a host built against
+                              an older header would otherwise hand the kernel a garbage step_error store target */
     const float* part;     /* pcdm_gemm_params.ws of the producing call */
     int32_t split_k, M, N, Npad;
     const float* bias;     /* [Npad] or NULL */
@@ -61,7 +64,7 @@ typedef struct pcdm_gn_splitk_src {
     int64_t ldr;
     void* pre_out;
     int32_t store_pre;
-    int32_t rowvec_step_count;    /* as pcdm_gemm_params.rowvec_step_count / step_error (ABI 4) */
+    int32_t rowvec_step_count;    /* as pcdm_gemm_params.rowvec_step_count / step_error (ABI 6) */
     int32_t* step_error;
 } pcdm_gn_splitk_src;
 int pcdm_groupnorm_splitk(const pcdm_gn_splitk_src* src, const void* x2, int C2, int B, int HW, int groups, float eps,
@@ -179,7 +182,7 @@ typedef struct pcdm_gemm_params {
                                    taps are all tap 0 is taken for ntaps <= 3 and refused (-1) at ntaps = 4 */
     int32_t tap_group_n;
 } pcdm_gemm_params;
-/* pcdm_version() == 5: the struct above STARTS with struct_size and ends with a3, lda3, tap_lut, tap_group_n (4: ended with rowvec_step_count, step_error; 3: no struct_size, ended with
+/* Since pcdm_version() == 5 the struct above STARTS with struct_size and ends with a3, lda3, tap_lut, tap_group_n (6 left it unchanged; 4: ended with rowvec_step_count, step_error; 3: no struct_size, ended with
  * ln_row_stats, row_stats_out, gn_stats_out, gn_stats_gs -- the last two are gone with the GroupNorm-statistics producer; 2: ended with
  * dup_rows; 1: with ln_eps).  Zero-initialise it (memset), set struct_size = sizeof(pcdm_gemm_params): the library compares it with its own and
  * returns -1 on a mismatch, so a host built against another header fails at its first call instead of having trailing fields misread.
@@ -250,10 +253,12 @@ int pcdm_attn_wide(const void* q, int64_t ldq, const void* k, int64_t ldk, const
 
 /* ---- K12 time / class embedding helpers.
  * pcdm_timestep_embedding: diffusers Timesteps(dim, flip_sin_to_cos, shift) (ref :184,677): out fp32 [B,dim];
- *   t read from DEVICE memory: t_dev[step_dev ? *step_dev : 0] (int64), broadcast over B.
+ *   t read from a DEVICE table of `rows` timesteps: t_dev[row] (int64), broadcast over B.  row = step_dev ? *step_dev : 0, bounded on the
+ *   device (ABI 6): a counter outside [0, rows) uses the nearest valid row and sets *step_error (may be NULL) to 1.  Returns -1 without
+ *   launching for a NULL t_dev / out, B or dim < 1, an odd dim, rows < 1 or a step_error that is not 4-byte aligned.
  * pcdm_small_linear: y[b,n] = act_out( sum_k act_in(x[b,k]) * W[n,k] + bias[n] ), x,y fp32, W bf16 [N,K],
  *   B <= 32; act_in: 1 = SiLU; act_out: 1 = SiLU before `add`, 2 = SiLU after `add`.  (TimestepEmbedding MLPs ref :191-197,247; every ResnetBlock2D.time_emb_proj) */
-int pcdm_timestep_embedding(const int64_t* t_dev, const int32_t* step_dev, float* out, int B, int dim,
+int pcdm_timestep_embedding(const int64_t* t_dev, int rows, const int32_t* step_dev, int32_t* step_error, float* out, int B, int dim,
                             int flip_sin_to_cos, float shift, pcdm_stream_t s);
 int pcdm_small_linear(const float* x, const void* w, const float* bias, const float* add, float* y, int B, int K,
                       int N, int act_in, int act_out, pcdm_stream_t s);
@@ -265,8 +270,9 @@ int pcdm_small_linear(const float* x, const void* w, const float* bias, const fl
 int pcdm_timestep_embedding_rows(const int64_t* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s);
 int pcdm_time_class_combine(const float* emb_t, const float* cls, void* out_bf16, int n, int B, int D, pcdm_stream_t s);
 /* float32-timestep forms (the fractional timesteps of the sigma-space samplers with timestep_spacing="linspace", e.g. 749.25): the SAME kernels
- * instantiated for a float table; the timestep is used as the fp32 value it is, so an integer-valued float gives the bits of the int64 form. */
-int pcdm_timestep_embedding_f32(const float* t_dev, const int32_t* step_dev, float* out, int B, int dim,
+ * instantiated for a float table; the timestep is used as the fp32 value it is, so an integer-valued float gives the bits of the int64 form.
+ * rows / step_dev / step_error of pcdm_timestep_embedding_f32: exactly as pcdm_timestep_embedding (bounded on the device, ABI 6). */
+int pcdm_timestep_embedding_f32(const float* t_dev, int rows, const int32_t* step_dev, int32_t* step_error, float* out, int B, int dim,
                                 int flip_sin_to_cos, float shift, pcdm_stream_t s);
 int pcdm_timestep_embedding_rows_f32(const float* t_dev, int n, float* out, int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s);
 
@@ -293,26 +299,35 @@ int pcdm_f32_to_bf16(const float* x, void* y, int64_t n, pcdm_stream_t s);
 
 /* ---- K13 CFG combine + scheduler step (stage2_inpaint_pipeline.py:510-519).
  * eps [2N or N, C*HW] fp32 (uncond rows first).  g = guidance scale (cfg=0: eps used as is).
- * x_prev = cx*x + ce*eps_guided (+ cn*noise); coefficients read from DEVICE table coef[step][4] =
- * {cx, ce, cn, unused} at index *step_dev so that one captured hipGraph serves every step.
- * Optionally writes the guided eps (eps_out) and x0 = c0x*x + c0e*eps is left to the host scheduler. */
+ * x_prev = cx*x + ce*eps_guided (+ cn*noise); coefficients read from row `row` of the DEVICE table coef[rows][4] =
+ * {cx, ce, cn, unused} so that one captured hipGraph serves every step.  row = step_dev ? *step_dev : 0, bounded on the device (ABI 6): a
+ * counter outside [0, rows) uses the nearest valid row and sets *step_error (may be NULL) to 1.
+ * Optionally writes the guided eps (eps_out) and x0 = c0x*x + c0e*eps is left to the host scheduler.
+ * coef == NULL (with x_prev == NULL: the CFG combine alone) reads no table: rows and step_error are then ignored and not checked.
+ * Returns -1 without launching for a NULL eps, n < 1, x_prev without x or coef, and with a table: rows < 1 or a step_error that is not
+ * 4-byte aligned. */
 int pcdm_cfg_step(const float* eps, int cfg, float g, const float* x, const float* noise, float* x_prev,
-                  float* eps_out, const float* coef, const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+                  float* eps_out, const float* coef, int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s);
 /* CFG combine + diffusers UniPCMultistepScheduler.step (the shipped driver's scheduler: stage2_batchtest_inpaint_model.py:132;
- * SURVEY.md Appendix A-10; solver order <= 2) as one kernel on static state, replayable from a hipGraph.  Row *step_dev of the DEVICE
- * table coef[step][12] = {a_x, a_e, use_corrector, c_last, c_m1, c_m2, c_mt, p_x, p_mt, p_m1, 0, 0}:
+ * SURVEY.md Appendix A-10; solver order <= 2) as one kernel on static state, replayable from a hipGraph.  Row `row` of the DEVICE
+ * table coef[rows][12] = {a_x, a_e, use_corrector, c_last, c_m1, c_m2, c_mt, p_x, p_mt, p_m1, 0, 0}:
  *   m_t = a_x x + a_e eps_guided;  x_c = use_corrector ? c_last last + c_m1 m1 + c_m2 m2 + c_mt m_t : x;  x' = p_x x_c + p_mt m_t + p_m1 m1
- * then, in place: x <- x', m2 <- m1, m1 <- m_t, last <- x_c (all fp32 [n]; zero m1 / m2 / last before step 0). */
+ * then, in place: x <- x', m2 <- m1, m1 <- m_t, last <- x_c (all fp32 [n]; zero m1 / m2 / last before step 0).
+ * row = step_dev ? *step_dev : 0, bounded on the device (ABI 6): a counter outside [0, rows) uses the nearest valid row and sets *step_error
+ * (may be NULL) to 1.  Returns -1 without launching for a NULL eps / state / coef pointer, n < 1, rows < 1 or a step_error that is not
+ * 4-byte aligned. */
 int pcdm_unipc_step(const float* eps, int cfg, float g, float* x, float* m1, float* m2, float* last, const float* coef,
-                    const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+                    int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s);
 /* CFG combine + DPMSolverMultistepScheduler.step ("DPM++ 2M" and its SDE form; dpmsolver++ / sde-dpmsolver++, solver order <= 2,
- * midpoint / heun) as one kernel on static state, replayable from a hipGraph.  Row *step_dev of the DEVICE table
- * coef[step][8] = {a_x, a_e, p_x, p_m0, p_m1, p_z, 0, 0}:
- *   m0 = a_x x + a_e eps_guided;  x' = p_x x + p_m0 m0 + p_m1 m1 + p_z noise_all[*step_dev][i]
- * then, in place: x <- x', m1 <- m0 (all fp32 [n]; zero m1 before step 0).  noise_all [steps, n] may be NULL when no row has
- * p_z != 0 (the term is then skipped).  step_dev NULL: row 0. */
+ * midpoint / heun) as one kernel on static state, replayable from a hipGraph.  Row `row` of the DEVICE table
+ * coef[rows][8] = {a_x, a_e, p_x, p_m0, p_m1, p_z, 0, 0}:
+ *   m0 = a_x x + a_e eps_guided;  x' = p_x x + p_m0 m0 + p_m1 m1 + p_z noise_all[row][i]
+ * then, in place: x <- x', m1 <- m0 (all fp32 [n]; zero m1 before step 0).  noise_all [rows, n] (as many rows as coef) may be NULL when
+ * no row has p_z != 0 (the term is then skipped).  row = step_dev ? *step_dev : 0, bounded on the device (ABI 6) before either table is
+ * addressed: a counter outside [0, rows) uses the nearest valid row and sets *step_error (may be NULL) to 1.  Returns -1 without launching
+ * for a NULL eps / state / coef pointer, n < 1, rows < 1 or a step_error that is not 4-byte aligned. */
 int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, float* m1, const float* noise_all, const float* coef,
-                    const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+                    int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s);
 /* CFG combine + one step of EulerDiscreteScheduler / EulerAncestralDiscreteScheduler / LMSDiscreteScheduler / PNDMScheduler (PLMS) as one
  * kernel on static state, replayable from a hipGraph: the four are linear maps on (x, a saved sample, eps and up to three older eps, noise)
  * with host-known scalars.  State, all fp32 [n], distinct buffers, zeroed before step 0: x, xs (saved sample), h1 / h2 / h3 (eps history,
@@ -347,10 +362,13 @@ int pcdm_multistep_step(const float* eps, int cfg, float g, float* x, float* xs,
  * x_prev = (c_x0*x0 + c_x*x + c_noise*noise) * out_scale + out_shift.  x_prev may alias x. */
 int pcdm_unclip_step(const float* pred, int cfg, float g, const float* x, const float* noise, float* x_prev,
                      const float* c8, int64_t n, pcdm_stream_t s);
-/* The same step with its eight coefficients read from row *step_dev of a DEVICE table coef[steps][8] and its noise from slab *step_dev
- * of noise_all [steps, n] (NULL: none), updating x in place: one captured hipGraph serves every step of the stage-1 loop. */
+/* The same step with its eight coefficients read from row `row` of a DEVICE table coef[rows][8] and its noise from slab `row`
+ * of noise_all [rows, n] (NULL: none), updating x in place: one captured hipGraph serves every step of the stage-1 loop.
+ * row = step_dev ? *step_dev : 0, bounded on the device (ABI 6) before either table is addressed: a counter outside [0, rows) uses the
+ * nearest valid row and sets *step_error (may be NULL) to 1.  Returns -1 without launching for a NULL pred / x / coef, n < 1, rows < 1 or a
+ * step_error that is not 4-byte aligned. */
 int pcdm_unclip_step_dev(const float* pred, int cfg, float g, float* x, const float* noise_all, const float* coef,
-                         const int32_t* step_dev, int64_t n, pcdm_stream_t s);
+                         int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s);
 /* rescale_noise_cfg (stage2_inpaint_pipeline.py:52-63): out = gr * cfg * std(text)/std(cfg) + (1-gr) * cfg, per sample
  * over n = C*H*W elements (unbiased std); cfg_eps / text_eps / out fp32 [N, n]; out may alias cfg_eps. */
 int pcdm_rescale_noise_cfg(const float* cfg_eps, const float* text_eps, float* out, int N, int64_t n,
@@ -371,7 +389,7 @@ int pcdm_gaussian_sample(const float* moments, const float* noise, float* out, i
 int pcdm_image_to_uint8(const float* x, void* out, int B, int cstride, int HW, pcdm_stream_t s);
 /* y = sum_i c[i] * x_i  (i < nin <= 6), fp32; UniPC predictor/corrector linear combinations. */
 int pcdm_lincomb(float* y, int nin, const float* const* xs, const float* c, int64_t n, pcdm_stream_t s);
-/* *step_dev += 1 */
+/* *step_dev += 1.  Reads no table: every reader of a table bounds the counter itself (ABI 6). */
 int pcdm_advance_step(int32_t* step_dev, pcdm_stream_t s);
 /* out NHWC bf16 [B, 2H, 2W, C] <- in [B * H * W, 4 * C] bf16 (columns = phase 2a + b major, then channel): out[b, 2y + a, 2x + bb, c] =
  * in[(b, y, x), (2a + bb) C + c].  The second half of the phase-decomposed Upsample2D convolution (pcdm_gemm_params.tap_lut).  C % 8 == 0. */
@@ -912,7 +930,7 @@ int pcdm_unet_set_shared_cfg_input(pcdm_unet* u, void* workspace, int shared);
  * pcdm_unet_forward calls on this workspace that pass the same t_dev and a device step counter pick their block by that counter; any other
  * call computes the embeddings per step as before.  Bit-identical to the per-step launches.  The table is keyed on the POINTER t_dev: a host
  * that rewrites the timestep buffer in place (another schedule or step count) must call pcdm_unet_prepare_timesteps again before the
- * next forward (not checkable at launch: it lives in device memory).  The device step counter must stay below n: ABI 4 bounds it on the
+ * next forward (not checkable at launch: it lives in device memory).  The device step counter must stay below n: ABI 6 bounds it on the
  * device (clamped into the table, error flag: pcdm_unet_step_overflow). */
 int64_t pcdm_unet_time_table_bytes(const pcdm_unet* u, int n, int B);
 int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, int n, void* table, void* workspace, pcdm_stream_t s);
@@ -920,7 +938,11 @@ int pcdm_unet_prepare_timesteps(pcdm_unet* u, const int64_t* t_dev, int n, void*
  * else as the int64 forms, and the same bits for integer-valued floats. */
 int pcdm_unet_prepare_timesteps_f32(pcdm_unet* u, const float* t_dev, int n, void* table, void* workspace, pcdm_stream_t s);
 /* x_in NHWC bf16 [B, h, w, conv_in.cin] (pcdm_assemble_input / pcdm_nchw_f32_to_nhwc_bf16); timestep = t_dev[step_dev ? *step_dev : 0] (device);
- * pose_b as passed to prepare_conditioning (0: no pose); eps_out fp32 NCHW [B, out_channels, h, w] */
+ * pose_b as passed to prepare_conditioning (0: no pose); eps_out fp32 NCHW [B, out_channels, h, w].
+ * KNOWN REMAINDER of the ABI 6 bound: these two calls take no length for t_dev.  With step_dev NULL they read t_dev[0] (length 1); with the
+ * t_dev of pcdm_unet_prepare_timesteps the counter is bounded into that table's n rows (pcdm_unet_step_overflow).  With a device counter but
+ * WITHOUT a table prepared for this t_dev the length is unknown to the library: *step_dev < length of t_dev stays the caller's contract (a
+ * negative counter reads row 0, no flag). */
 int pcdm_unet_forward(pcdm_unet* u, const void* x_in, const int64_t* t_dev, const int32_t* step_dev, int B, int h, int w, int L, int pose_b,
                       void* workspace, float* eps_out, pcdm_stream_t s);
 int pcdm_unet_forward_f32(pcdm_unet* u, const void* x_in, const float* t_dev, const int32_t* step_dev, int B, int h, int w, int L, int pose_b,

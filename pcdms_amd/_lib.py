@@ -55,10 +55,14 @@ class GemmParams(C.Structure):
 class GnSplitKSrc(C.Structure):
     """Mirror of ``pcdm_gn_splitk_src`` (include/pcdm.h)."""
 
-    _fields_ = [("part", C.c_void_p), ("split_k", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("Npad", C.c_int32),
+    _fields_ = [("struct_size", C.c_uint32), ("part", C.c_void_p), ("split_k", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("Npad", C.c_int32),
                 ("bias", C.c_void_p), ("rowvec", C.c_void_p), ("ldrv", C.c_int64), ("rowvec_step", C.c_void_p), ("rowvec_step_stride", C.c_int64),
                 ("residual", C.c_void_p), ("ldr", C.c_int64), ("pre_out", C.c_void_p), ("store_pre", C.c_int32),
                 ("rowvec_step_count", C.c_int32), ("step_error", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(GnSplitKSrc)   # (ABI 6: pcdm_groupnorm_splitk refuses a struct of another size)
 
 
 class UNetConfig(C.Structure):
@@ -128,9 +132,9 @@ _SIGS = {
     "pcdm_quantize_fp8": ([_P, _P, _L, _I, _I, _L, _L, _F, _P], C.c_int),
     "pcdm_flash_attn_fp8": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _F, _F, _F, _P], C.c_int),
     "pcdm_attn_wide": ([_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P], C.c_int),
-    "pcdm_timestep_embedding": ([_P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
+    "pcdm_timestep_embedding": ([_P, _I, _P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding_rows": ([_P, _I, _P, _I, _I, _F, _P], C.c_int),
-    "pcdm_timestep_embedding_f32": ([_P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
+    "pcdm_timestep_embedding_f32": ([_P, _I, _P, _P, _P, _I, _I, _I, _F, _P], C.c_int),
     "pcdm_timestep_embedding_rows_f32": ([_P, _I, _P, _I, _I, _F, _P], C.c_int),
     "pcdm_time_class_combine": ([_P, _P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_small_linear": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
@@ -139,12 +143,12 @@ _SIGS = {
     "pcdm_nchw_f32_to_nhwc_bf16": ([_P, _P, _I, _I, _I, _I, _P], C.c_int),
     "pcdm_nhwc_bf16_to_nchw_f32": ([_P, _P, _I, _I, _I, _P], C.c_int),
     "pcdm_f32_to_bf16": ([_P, _P, _L, _P], C.c_int),
-    "pcdm_cfg_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
-    "pcdm_unipc_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P], C.c_int),
-    "pcdm_dpmpp_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_cfg_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
+    "pcdm_unipc_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
+    "pcdm_dpmpp_step": ([_P, _I, _F, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
     "pcdm_multistep_step": ([_P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
     "pcdm_unclip_step": ([_P, _I, _F, _P, _P, _P, C.POINTER(_F), _L, _P], C.c_int),
-    "pcdm_unclip_step_dev": ([_P, _I, _F, _P, _P, _P, _P, _L, _P], C.c_int),
+    "pcdm_unclip_step_dev": ([_P, _I, _F, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
     "pcdm_lincomb": ([_P, _I, C.POINTER(_P), C.POINTER(_F), _L, _P], C.c_int),
     "pcdm_rescale_noise_cfg": ([_P, _P, _P, _I, _L, _F, _P], C.c_int),
     "pcdm_softmax_rows": ([_P, _P, _I, _I, _L, _L, _F, _P], C.c_int),

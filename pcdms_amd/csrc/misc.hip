@@ -7,16 +7,27 @@
 #include "image_common.h"
 
 namespace {
+// the device step counter bounded into a table of `rows` rows (NULL counter: row 0), as pcdm_gemm_detail::bounded_step: a value outside
+// [0, rows) reads the nearest valid row instead of foreign memory and raises *err (every lane stores the same 1: a benign race)
+__device__ __forceinline__ int table_row(const int32_t* step_dev, int rows, int32_t* err) {
+    int st = step_dev ? *step_dev : 0;
+    if (st < 0 || st >= rows) {
+        if (err) *err = 1;
+        st = st < 0 ? 0 : rows - 1;
+    }
+    return st;
+}
+
 // out[b, j]: diffusers Timesteps (flip_sin_to_cos => [cos | sin]).  T = int64_t (the integer schedules) or float (the fractional timesteps of
 // the sigma-space samplers): the timestep is converted to fp32 once and the arithmetic is the same, so an integer-valued float gives the bits
 // of the int64 form.
 template <typename T>
-__global__ void timestep_embedding_kernel(const T* __restrict__ t_dev, const int32_t* __restrict__ step_dev,
-                                          float* __restrict__ out, int B, int dim, int flip, float shift) {
+__global__ void timestep_embedding_kernel(const T* __restrict__ t_dev, int rows, const int32_t* __restrict__ step_dev,
+                                          int32_t* __restrict__ step_error, float* __restrict__ out, int B, int dim, int flip, float shift) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * dim) return;
     const int j = i % dim, half = dim / 2;
-    const float tv = (float)t_dev[step_dev ? *step_dev : 0];
+    const float tv = (float)t_dev[table_row(step_dev, rows, step_error)];
     const int kk = j < half ? j : j - half;
     const float f = expf(-9.210340371976184f * (float)kk / ((float)half - shift));
     const float a = tv * f;
@@ -99,17 +110,6 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restri
     }
 }
 
-// the device step counter bounded into a table of `rows` rows (NULL counter: row 0), as pcdm_gemm_detail::bounded_step: a value outside
-// [0, rows) reads the nearest valid row instead of foreign memory and raises *err (every lane stores the same 1: a benign race)
-__device__ __forceinline__ int table_row(const int32_t* step_dev, int rows, int32_t* err) {
-    int st = step_dev ? *step_dev : 0;
-    if (st < 0 || st >= rows) {
-        if (err) *err = 1;
-        st = st < 0 ? 0 : rows - 1;
-    }
-    return st;
-}
-
 // scale_tab != NULL (pcdm_assemble_input_ex): the LATENT channels are multiplied in fp32 by scale_tab[row * scale_stride + scale_col]
 // (scheduler.scale_model_input) before their one rounding to bf16; NULL: pcdm_assemble_input, bit for bit
 __global__ void assemble_input_kernel(const float* __restrict__ latents, int N, int rep,
@@ -176,11 +176,12 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ x, u16* __restrict_
 
 __global__ void cfg_step_kernel(const float* __restrict__ eps, int cfg, float g, const float* __restrict__ x,
                                 const float* __restrict__ noise, float* __restrict__ x_prev,
-                                float* __restrict__ eps_out, const float* __restrict__ coef,
-                                const int32_t* __restrict__ step_dev, int64_t n) {
+                                float* __restrict__ eps_out, const float* __restrict__ coef, int rows,
+                                const int32_t* __restrict__ step_dev, int32_t* __restrict__ step_error, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float* cf = coef + 4 * (step_dev ? *step_dev : 0);
+    // coef NULL (CFG combine only): no table, no row, the flag is not touched
+    const float* cf = coef ? coef + 4 * table_row(step_dev, rows, step_error) : nullptr;
     float e = eps[i];
     if (cfg) e = e + g * (eps[n + i] - e);
     if (eps_out) eps_out[i] = e;
@@ -199,11 +200,11 @@ __global__ void cfg_step_kernel(const float* __restrict__ eps, int cfg, float g,
 //   x'    = c[7] x_c + c[8] m_t + c[9] m1                        (predictor, after the history shift m_t -> m1 -> m2)
 // and the state advances in place: x <- x', m2 <- m1, m1 <- m_t, last <- x_c.  Every element is owned by one thread.
 __global__ void unipc_step_kernel(const float* __restrict__ eps, int cfg, float g, float* __restrict__ x, float* __restrict__ m1,
-                                  float* __restrict__ m2, float* __restrict__ last, const float* __restrict__ coef,
-                                  const int32_t* __restrict__ step_dev, int64_t n) {
+                                  float* __restrict__ m2, float* __restrict__ last, const float* __restrict__ coef, int rows,
+                                  const int32_t* __restrict__ step_dev, int32_t* __restrict__ step_error, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float* c = coef + 12 * (step_dev ? *step_dev : 0);
+    const float* c = coef + 12 * table_row(step_dev, rows, step_error);
     float e = eps[i];
     if (cfg) e = e + g * (eps[n + i] - e);
     const float xi = x[i], a1 = m1[i], a2 = m2[i];
@@ -223,11 +224,11 @@ __global__ void unipc_step_kernel(const float* __restrict__ eps, int cfg, float 
 //   x' = p_x x + p_m0 m0 + p_m1 m1 + p_z noise_all[*step_dev, i] (noise_all NULL: no noise term)
 // then, in place: x <- x', m1 <- m0.  Every element is owned by one thread.
 __global__ void dpmpp_step_kernel(const float* __restrict__ eps, int cfg, float g, float* __restrict__ x, float* __restrict__ m1,
-                                  const float* __restrict__ noise_all, const float* __restrict__ coef,
-                                  const int32_t* __restrict__ step_dev, int64_t n) {
+                                  const float* __restrict__ noise_all, const float* __restrict__ coef, int rows,
+                                  const int32_t* __restrict__ step_dev, int32_t* __restrict__ step_error, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int st = step_dev ? *step_dev : 0;
+    const int st = table_row(step_dev, rows, step_error);
     const float* c = coef + 8 * st;
     float e = eps[i];
     if (cfg) e = e + g * (eps[n + i] - e);
@@ -335,11 +336,11 @@ __global__ void unclip_step_kernel(const float* __restrict__ pred, int cfg, floa
 
 // the same with the step's eight coefficients and its noise slab taken from DEVICE tables at *step_dev (hipGraph-replayable stage-1 loop)
 __global__ void unclip_step_dev_kernel(const float* __restrict__ pred, int cfg, float g, float* __restrict__ x,
-                                       const float* __restrict__ noise_all, const float* __restrict__ coef,
-                                       const int32_t* __restrict__ step_dev, int64_t n) {
+                                       const float* __restrict__ noise_all, const float* __restrict__ coef, int rows,
+                                       const int32_t* __restrict__ step_dev, int32_t* __restrict__ step_error, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int st = *step_dev;
+    const int st = table_row(step_dev, rows, step_error);
     const float* c = coef + 8 * st;
     float e = pred[i];
     if (cfg) e = e + g * (pred[n + i] - e);
@@ -489,7 +490,7 @@ __global__ void advance_step_kernel(int32_t* step) {
 }
 }  // namespace
 
-extern "C" int pcdm_version(void) { return PCDM_ABI_VERSION; }   // 5: pcdm_gemm_params starts with struct_size, ends with a3 / lda3 (include/pcdm.h)
+extern "C" int pcdm_version(void) { return PCDM_ABI_VERSION; }   // 6: every step-indexed table read takes its row count and an error flag (include/pcdm.h)
 extern "C" int pcdm_is_emulator(void) {
 #ifdef PCDM_EMU
     return 1;
@@ -498,20 +499,20 @@ extern "C" int pcdm_is_emulator(void) {
 #endif
 }
 
-extern "C" int pcdm_timestep_embedding(const int64_t* t_dev, const int32_t* step_dev, float* out, int B, int dim,
-                                       int flip_sin_to_cos, float shift, pcdm_stream_t s) {
-    if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2) return -1;
-    PCDM_LAUNCH(timestep_embedding_kernel<int64_t>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, step_dev,
-                out, B, dim, flip_sin_to_cos, shift);
+extern "C" int pcdm_timestep_embedding(const int64_t* t_dev, int rows, const int32_t* step_dev, int32_t* step_error, float* out, int B,
+                                       int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s) {
+    if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2 || rows < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(timestep_embedding_kernel<int64_t>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, rows, step_dev,
+                step_error, out, B, dim, flip_sin_to_cos, shift);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int pcdm_timestep_embedding_f32(const float* t_dev, const int32_t* step_dev, float* out, int B, int dim,
-                                           int flip_sin_to_cos, float shift, pcdm_stream_t s) {
-    if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2) return -1;
-    PCDM_LAUNCH(timestep_embedding_kernel<float>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, step_dev,
-                out, B, dim, flip_sin_to_cos, shift);
+extern "C" int pcdm_timestep_embedding_f32(const float* t_dev, int rows, const int32_t* step_dev, int32_t* step_error, float* out, int B,
+                                           int dim, int flip_sin_to_cos, float shift, pcdm_stream_t s) {
+    if (!t_dev || !out || B <= 0 || dim <= 0 || dim % 2 || rows < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(timestep_embedding_kernel<float>, grid1d((int64_t)B * dim, 256), dim3(256), 0, (hipStream_t)s, t_dev, rows, step_dev,
+                step_error, out, B, dim, flip_sin_to_cos, shift);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -594,26 +595,30 @@ extern "C" int pcdm_f32_to_bf16(const float* x, void* y, int64_t n, pcdm_stream_
 }
 
 extern "C" int pcdm_cfg_step(const float* eps, int cfg, float g, const float* x, const float* noise, float* x_prev,
-                             float* eps_out, const float* coef, const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
+                             float* eps_out, const float* coef, int rows, const int32_t* step_dev, int32_t* step_error, int64_t n,
+                             pcdm_stream_t s) {
     if (!eps || n <= 0 || (x_prev && (!x || !coef))) return -1;
+    if (coef && (rows < 1 || ((uintptr_t)step_error & 3))) return -1;   // coef NULL: no table is read, rows / step_error are ignored
     PCDM_LAUNCH(cfg_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, noise, x_prev, eps_out,
-                coef, step_dev, n);
+                coef, rows, step_dev, step_error, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int pcdm_unipc_step(const float* eps, int cfg, float g, float* x, float* m1, float* m2, float* last, const float* coef,
-                               const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
-    if (!eps || !x || !m1 || !m2 || !last || !coef || n <= 0) return -1;
-    PCDM_LAUNCH(unipc_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, m2, last, coef, step_dev, n);
+                               int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s) {
+    if (!eps || !x || !m1 || !m2 || !last || !coef || n <= 0 || rows < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(unipc_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, m2, last, coef, rows, step_dev,
+                step_error, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int pcdm_dpmpp_step(const float* eps, int cfg, float g, float* x, float* m1, const float* noise_all, const float* coef,
-                               const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
-    if (!eps || !x || !m1 || !coef || n <= 0) return -1;
-    PCDM_LAUNCH(dpmpp_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, noise_all, coef, step_dev, n);
+                               int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s) {
+    if (!eps || !x || !m1 || !coef || n <= 0 || rows < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(dpmpp_step_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, eps, cfg, g, x, m1, noise_all, coef, rows, step_dev,
+                step_error, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }
@@ -639,9 +644,10 @@ extern "C" int pcdm_unclip_step(const float* pred, int cfg, float g, const float
 }
 
 extern "C" int pcdm_unclip_step_dev(const float* pred, int cfg, float g, float* x, const float* noise_all, const float* coef,
-                                    const int32_t* step_dev, int64_t n, pcdm_stream_t s) {
-    if (!pred || !x || !coef || !step_dev || n <= 0) return -1;
-    PCDM_LAUNCH(unclip_step_dev_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, pred, cfg, g, x, noise_all, coef, step_dev, n);
+                                    int rows, const int32_t* step_dev, int32_t* step_error, int64_t n, pcdm_stream_t s) {
+    if (!pred || !x || !coef || n <= 0 || rows < 1 || ((uintptr_t)step_error & 3)) return -1;
+    PCDM_LAUNCH(unclip_step_dev_kernel, grid1d(n, 256), dim3(256), 0, (hipStream_t)s, pred, cfg, g, x, noise_all, coef, rows, step_dev,
+                step_error, n);
     PCDM_CHECK_LAUNCH();
     return 0;
 }

@@ -1001,7 +1001,8 @@ extern "C" int pcdm_groupnorm(const void* x1, int C1, const void* x2, int C2, in
 
 extern "C" int pcdm_groupnorm_splitk(const pcdm_gn_splitk_src* p, const void* x2, int C2, int B, int HW, int groups, float eps,
                                      const float* gamma, const float* beta, int fuse_silu, void* y, float* ws, pcdm_stream_t s) {
-    if (!p || !p->part || !p->pre_out || !y || !ws || B <= 0 || HW <= 0 || groups <= 0 || groups > 256) return -1;
+    if (!p || p->struct_size != (uint32_t)sizeof(pcdm_gn_splitk_src)) return -1;   // a host built against another header: refused before any other field is read
+    if (!p->part || !p->pre_out || !y || !ws || B <= 0 || HW <= 0 || groups <= 0 || groups > 256) return -1;
     const int C1 = p->N, C = C1 + C2;
     if (C1 <= 0 || C1 % 8 || C2 % 8 || C % groups || C > kGnMaxC || (C2 > 0 && !x2)) return -1;
     if (p->split_k < 2 || p->split_k > 64 || p->Npad < C1 || p->Npad % 8 || p->M != B * HW) return -1;

@@ -273,6 +273,7 @@ struct Run {   // one forward / conditioning pass: helpers around the C-ABI call
             !getenv_off("PCDM_DEFER_SPLITK")) {
             p.defer_reduce = 1;
             memset(&pend, 0, sizeof(pend));
+            pend.struct_size = (uint32_t)sizeof(pend);
             pend.part = p.ws; pend.split_k = p.split_k; pend.M = M; pend.N = w->N; pend.Npad = w->Npad;
             pend.bias = p.bias; pend.rowvec = p.rowvec; pend.ldrv = g.rowvec ? (g.ldrv ? g.ldrv : w->N) : 0;
             pend.rowvec_step = p.rowvec_step; pend.rowvec_step_stride = p.rowvec_step_stride;
@@ -770,8 +771,11 @@ static int unet_forward_impl(pcdm_unet* u, const void* x_in, const void* t_dev, 
     const int rv_count = use_table ? cit->second.time_steps : 0;          // the step counter is bounded into the table on the device (ABI 4)
     int32_t* rv_err = use_table ? R.buf<int32_t>("step_err") : nullptr;
     if (!use_table) {
-        R.chk(t_f32 ? pcdm_timestep_embedding_f32((const float*)t_dev, step_dev, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s)
-                    : pcdm_timestep_embedding((const int64_t*)t_dev, step_dev, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s),
+        // the length of t_dev this path knows: 1 without a counter; with a counter and no table prepared for this t_dev the caller's contract
+        // (counter < length of t_dev) is all there is -- INT32_MAX leaves the counter as it is, a negative one reads row 0 (include/pcdm.h)
+        const int t_rows = step_dev ? INT32_MAX : 1;
+        R.chk(t_f32 ? pcdm_timestep_embedding_f32((const float*)t_dev, t_rows, step_dev, nullptr, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s)
+                    : pcdm_timestep_embedding((const int64_t*)t_dev, t_rows, step_dev, nullptr, R.buf<float>("t_emb"), B, C0, c.flip_sin_to_cos, c.freq_shift, s),
               "pcdm_timestep_embedding");
         const PW *t1 = R.pw("time_embedding.linear_1"), *t2 = R.pw("time_embedding.linear_2");
         if (R.rc) return R.rc;

@@ -779,14 +779,16 @@ def flash_attn_fp8(q: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, out: to
 
 # ------------------------------------------------------------------------------------ small ops
 def timestep_embedding(t_dev: torch.Tensor, step_dev: Optional[torch.Tensor], out: torch.Tensor, flip: bool = True,
-                       shift: float = 0.0) -> torch.Tensor:
-    """t_dev: int64 or float32 device table (a float table keeps its fractional timesteps: ``pcdm_timestep_embedding_f32``)."""
+                       shift: float = 0.0, step_error: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """t_dev: int64 or float32 device table (a float table keeps its fractional timesteps: ``pcdm_timestep_embedding_f32``).  The counter is
+    bounded into the table's ``t_dev.numel()`` rows on the device; a counter outside it sets ``step_error`` (int32 device tensor) to 1."""
     assert t_dev.dtype in (torch.int64, torch.float32) and t_dev.is_contiguous() and t_dev.numel() >= 1
     assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2
-    _cn(step_dev, torch.int32, 1, "step_dev")
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
     B, dim = out.shape
     fn = _lib.lib().pcdm_timestep_embedding if t_dev.dtype == torch.int64 else _lib.lib().pcdm_timestep_embedding_f32
-    _chk(fn(_ptr(t_dev), _ptr(step_dev), _ptr(out), B, dim, int(flip), shift, _stream(out)), "pcdm_timestep_embedding")
+    _chk(fn(_ptr(t_dev), t_dev.numel(), _ptr(step_dev), _ptr(step_error), _ptr(out), B, dim, int(flip), shift, _stream(out)),
+         "pcdm_timestep_embedding")
     return out
 
 
@@ -894,44 +896,52 @@ def f32_to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
 
 def cfg_step(eps: torch.Tensor, cfg: bool, g: float, x: Optional[torch.Tensor], x_prev: Optional[torch.Tensor],
              coef: Optional[torch.Tensor], step_dev: Optional[torch.Tensor] = None,
-             noise: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None) -> None:
+             noise: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None,
+             step_error: Optional[torch.Tensor] = None) -> None:
+    """pcdm_cfg_step: coef fp32 [rows, 4] on the device (None: the CFG combine alone, no table); the counter is bounded into its rows on the
+    device and a counter outside them sets ``step_error`` (int32 device tensor) to 1."""
     n = eps.numel() // (2 if cfg else 1)
     _c(eps, torch.float32)
     assert eps.numel() == (2 * n if cfg else n) and n >= 1
     for what, t in (("x", x), ("noise", noise), ("x_prev", x_prev), ("eps_out", eps_out)):
         assert t is None or _c(t, torch.float32).numel() == n, (what, t.numel(), n)
     assert (x_prev is None) == (x is None) == (coef is None), "x, x_prev and coef come together (eps_out alone: the CFG combine only)"
-    _cn(coef, torch.float32, 4, "coef"); _cn(step_dev, torch.int32, 1, "step_dev")
-    assert coef is None or coef.numel() % 4 == 0
+    _cn(coef, torch.float32, 4, "coef"); _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
+    assert coef is None or (coef.dim() == 2 and coef.shape[1] == 4), "coef is [rows, 4]"
     _chk(_lib.lib().pcdm_cfg_step(_ptr(eps), int(cfg), g, _ptr(x), _ptr(noise), _ptr(x_prev), _ptr(eps_out),
-                                  _ptr(coef), _ptr(step_dev), n, _stream(eps)), "pcdm_cfg_step")
+                                  _ptr(coef), 0 if coef is None else coef.shape[0], _ptr(step_dev), _ptr(step_error), n, _stream(eps)),
+         "pcdm_cfg_step")
 
 
 def unipc_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torch.Tensor, m2: torch.Tensor, last: torch.Tensor,
-               coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None) -> None:
-    """pcdm_unipc_step: CFG combine + one UniPC step in place on (x, m1, m2, last); coef fp32 [steps, 12] on the device."""
+               coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None, step_error: Optional[torch.Tensor] = None) -> None:
+    """pcdm_unipc_step: CFG combine + one UniPC step in place on (x, m1, m2, last); coef fp32 [rows, 12] on the device.  The counter is bounded
+    into the rows on the device; a counter outside them sets ``step_error`` (int32 device tensor) to 1."""
     n = x.numel()
     for t in (eps, x, m1, m2, last, coef):
         _c(t, torch.float32)
-    assert eps.numel() == (2 * n if cfg else n) and m1.numel() == m2.numel() == last.numel() == n and coef.shape[-1] == 12
-    _cn(step_dev, torch.int32, 1, "step_dev")
-    _chk(_lib.lib().pcdm_unipc_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(m2), _ptr(last), _ptr(coef),
-                                    _ptr(step_dev), n, _stream(x)), "pcdm_unipc_step")
+    assert eps.numel() == (2 * n if cfg else n) and m1.numel() == m2.numel() == last.numel() == n
+    assert coef.dim() == 2 and coef.shape[1] == 12, "coef is [rows, 12]"
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
+    _chk(_lib.lib().pcdm_unipc_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(m2), _ptr(last), _ptr(coef), coef.shape[0],
+                                    _ptr(step_dev), _ptr(step_error), n, _stream(x)), "pcdm_unipc_step")
 
 
 def dpmpp_step(eps: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, m1: torch.Tensor, noise_all: Optional[torch.Tensor],
-               coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None) -> None:
-    """pcdm_dpmpp_step: CFG combine + one DPM-Solver++ step in place on (x, m1); coef fp32 [steps, 8], noise_all fp32
-    [steps, x.numel()] (or None), both on the device."""
+               coef: torch.Tensor, step_dev: Optional[torch.Tensor] = None, step_error: Optional[torch.Tensor] = None) -> None:
+    """pcdm_dpmpp_step: CFG combine + one DPM-Solver++ step in place on (x, m1); coef fp32 [rows, 8], noise_all fp32
+    [rows, x.numel()] (or None), both on the device.  The counter is bounded into the rows on the device; a counter outside them sets
+    ``step_error`` (int32 device tensor) to 1."""
     n = x.numel()
     for t in (eps, x, m1, coef):
         _c(t, torch.float32)
-    assert eps.numel() == (2 * n if cfg else n) and m1.numel() == n and coef.shape[-1] == 8
-    _cn(step_dev, torch.int32, 1, "step_dev")
+    assert eps.numel() == (2 * n if cfg else n) and m1.numel() == n
+    assert coef.dim() == 2 and coef.shape[1] == 8, "coef is [rows, 8]"
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
     if noise_all is not None:
-        assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
-    _chk(_lib.lib().pcdm_dpmpp_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(noise_all), _ptr(coef),
-                                    _ptr(step_dev), n, _stream(x)), "pcdm_dpmpp_step")
+        assert tuple(_c(noise_all, torch.float32).shape) == (coef.shape[0], n), "noise_all is [rows, n] with the rows of coef"
+    _chk(_lib.lib().pcdm_dpmpp_step(_ptr(eps), int(cfg), float(g), _ptr(x), _ptr(m1), _ptr(noise_all), _ptr(coef), coef.shape[0],
+                                    _ptr(step_dev), _ptr(step_error), n, _stream(x)), "pcdm_dpmpp_step")
 
 
 #: row layout of the ``pcdm_multistep_step`` table (include/pcdm.h PCDM_MS_*)
@@ -971,16 +981,18 @@ def unclip_step(pred: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, noise:
 
 
 def unclip_step_dev(pred: torch.Tensor, cfg: bool, g: float, x: torch.Tensor, noise_all: Optional[torch.Tensor], coef: torch.Tensor,
-                    step_dev: torch.Tensor) -> None:
-    """pcdm_unclip_step_dev: in place on x; coef fp32 [steps, 8], noise_all fp32 [steps, x.numel()] (or None), both on the device."""
+                    step_dev: Optional[torch.Tensor], step_error: Optional[torch.Tensor] = None) -> None:
+    """pcdm_unclip_step_dev: in place on x; coef fp32 [rows, 8], noise_all fp32 [rows, x.numel()] (or None), both on the device.  The counter
+    is bounded into the rows on the device; a counter outside them sets ``step_error`` (int32 device tensor) to 1."""
     _c(pred, torch.float32); _c(x, torch.float32); _c(coef, torch.float32)
     n = x.numel()
-    assert pred.numel() == (2 * n if cfg else n) and coef.shape[-1] == 8
-    _cn(step_dev, torch.int32, 1, "step_dev")
+    assert pred.numel() == (2 * n if cfg else n)
+    assert coef.dim() == 2 and coef.shape[1] == 8, "coef is [rows, 8]"
+    _cn(step_dev, torch.int32, 1, "step_dev"); _cn(step_error, torch.int32, 1, "step_error")
     if noise_all is not None:
-        assert _c(noise_all, torch.float32).numel() == coef.shape[0] * n
-    _chk(_lib.lib().pcdm_unclip_step_dev(_ptr(pred), int(cfg), float(g), _ptr(x), _ptr(noise_all), _ptr(coef), _ptr(step_dev), n,
-                                         _stream(x)), "pcdm_unclip_step_dev")
+        assert tuple(_c(noise_all, torch.float32).shape) == (coef.shape[0], n), "noise_all is [rows, n] with the rows of coef"
+    _chk(_lib.lib().pcdm_unclip_step_dev(_ptr(pred), int(cfg), float(g), _ptr(x), _ptr(noise_all), _ptr(coef), coef.shape[0],
+                                         _ptr(step_dev), _ptr(step_error), n, _stream(x)), "pcdm_unclip_step_dev")
 
 
 def lincomb(out: torch.Tensor, xs: Sequence[torch.Tensor], cs: Sequence[float]) -> torch.Tensor:

@@ -316,13 +316,13 @@ class Stage2_InpaintDiffusionPipeline:
             ops.rescale_noise_cfg(st["eps_g"], eps[n:], st["eps_g"], st["gr"])
             cfg, g, e = False, 1.0, st["eps_g"]
         if st["unipc"]:
-            ops.unipc_step(e, cfg, g, st["lat"], st["m1"], st["m2"], st["last"], st["coef"], st["step"])
+            ops.unipc_step(e, cfg, g, st["lat"], st["m1"], st["m2"], st["last"], st["coef"], st["step"], st["step_err"])
         elif st["dpm"]:
-            ops.dpmpp_step(e, cfg, g, st["lat"], st["m1"], st["noise"], st["coef"], st["step"])
+            ops.dpmpp_step(e, cfg, g, st["lat"], st["m1"], st["noise"], st["coef"], st["step"], st["step_err"])
         elif st.get("ms"):
             ops.multistep_step(e, cfg, g, st["lat"], st["xs"], st["h1"], st["h2"], st["h3"], st["noise"], st["coef"], st["step"], st["step_err"])
         else:
-            ops.cfg_step(e, cfg, g, st["lat"], st["lat"], st["coef"], st["step"])
+            ops.cfg_step(e, cfg, g, st["lat"], st["lat"], st["coef"], st["step"], step_error=st["step_err"])
         ops.advance_step(st["step"])
 
     @staticmethod
@@ -374,15 +374,15 @@ class Stage2_InpaintDiffusionPipeline:
                       eps_g=torch.empty_like(lat),
                       x_in=torch.empty(B, h, w, 64, dtype=ops.BF16, device=dev),
                       step=torch.zeros(1, dtype=torch.int32, device=dev),
+                      step_err=torch.zeros(1, dtype=torch.int32, device=dev),   # raised by every table reader for a counter outside its table
                       timesteps=torch.empty(n, dtype=tdt, device=dev),
                       coef=torch.empty(n, 12 if (unipc or ms) else 8 if dpm else 4, dtype=torch.float32, device=dev))
             if unipc:   # UniPC history (two stored x0-predictions, last corrected sample): static slots, zeroed per call
                 st.update(m1=torch.zeros_like(lat), m2=torch.zeros_like(lat), last=torch.zeros_like(lat))
             if dpm:     # DPM-Solver++ history (the previous x0-prediction) and, for the SDE form, the per-step noise table [n, numel]
                 st.update(m1=torch.zeros_like(lat), noise=torch.empty(n, lat.numel(), dtype=torch.float32, device=dev) if sde else None)
-            if ms:      # saved sample + three eps-history slots, zeroed per call; the flag the table readers raise for a counter outside the table
+            if ms:      # saved sample + three eps-history slots, zeroed per call
                 st.update(xs=torch.zeros_like(lat), h1=torch.zeros_like(lat), h2=torch.zeros_like(lat), h3=torch.zeros_like(lat),
-                          step_err=torch.zeros(1, dtype=torch.int32, device=dev),
                           noise=torch.empty(n, lat.numel(), dtype=torch.float32, device=dev) if sde else None)
             self._graph = None
         # Per call: the static input slots the captured step reads are refilled, and the step-invariant conditioning (class
@@ -395,8 +395,7 @@ class Stage2_InpaintDiffusionPipeline:
             st["mask"].copy_(mask)
         st["masked"].copy_(masked)
         st["timesteps"].copy_(timesteps.to(dev, tdt))
-        if ms:
-            st["step_err"].zero_()
+        st["step_err"].zero_()
         # (with the timestep table: the time / class embedding MLPs and every time_emb_proj for ALL steps, once per call)
         st["cond"] = unet.prepare_conditioning(B, h, w, feature_f, prior_embed, pose_cond, zero_ctx_batches=n0, shared_cfg_input=shared_halves,
                                                timesteps=st["timesteps"])
@@ -485,16 +484,15 @@ class Stage2_InpaintDiffusionPipeline:
         out = st["lat"].clone()
         # the device step counter indexes the per-call time table inside the UNet's kernels: they bound it (a counter beyond the table is
         # clamped, never an out-of-bounds read of THAT table) and raise a flag -- read once per sampling call (one 4-byte copy behind the
-        # loop).  The table-step samplers' kernels clamp and report likewise (st["step_err"]); pcdm_cfg_step / pcdm_unipc_step /
-        # pcdm_dpmpp_step do NOT bound their coefficient row, so by the time this error is raised on DDIM, UniPC or DPM-Solver++ a step has
-        # read past st["coef"].  The flag lives where
+        # loop).  Every sampler's step kernel bounds its coefficient / noise row and reports likewise (st["step_err"]: one more 4-byte read
+        # per call, no launch in the step), so no step of any sampler kind reads past st["coef"] or st["noise"].  The UNet's flag lives where
         # the schedule that ran keeps it: in the context's workspace on the C schedule (no kernel of such a call writes the Python
         # schedule's), in the UNet's scratch otherwise -- one 4-byte read per call either way, no second synchronisation
         if st["ctx"] is not None:
             overflow = st["ctx"].step_overflow(B, h, w, L=feature_f.shape[1])
         else:
             overflow = hasattr(unet, "step_overflow") and unet.step_overflow()
-        if overflow or (ms and int(st["step_err"].item()) != 0):
+        if overflow or int(st["step_err"].item()) != 0:
             raise RuntimeError("the device step counter left the time-embedding table of this sampling call (clamped on the device): "
                                "the schedule ran more steps than prepare_conditioning(timesteps=...) was given")
         return out

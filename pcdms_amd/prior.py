@@ -193,7 +193,8 @@ class Stage1_PriorTransformer(HipModel):
     @torch.no_grad()
     def forward(self, hidden_states, timestep: Union[torch.Tensor, float, int], proj_embedding, encoder_hidden_states,
                 encoder_hidden_states1, attention_mask=None, return_dict: bool = True,
-                do_classifier_free_guidance: bool = False, test_flag: bool = False, _step_dev: Optional[torch.Tensor] = None):
+                do_classifier_free_guidance: bool = False, test_flag: bool = False, _step_dev: Optional[torch.Tensor] = None,
+                _step_err: Optional[torch.Tensor] = None):
         if attention_mask is not None:
             raise NotImplementedError("attention_mask: the reference's only call site passes None (stage1_prior_pipeline.py:464)")
         if test_flag:
@@ -219,7 +220,8 @@ class Stage1_PriorTransformer(HipModel):
         self._static_tokens(tokens, proj_embedding, encoder_hidden_states, encoder_hidden_states1, B)
         # time token: sinusoid -> Linear+SiLU -> Linear (+ positional row 3)
         tap = self._tap   # test hook (HipModel._tap): a no-op unless ``self._taps`` is a dict
-        sin = ops.timestep_embedding(t_dev, _step_dev, self._buf("sin", (B, D), torch.float32), flip=True, shift=0.0)
+        # (the counter is bounded into the table on the device; one outside it raises ``_step_err``, a device int32 flag)
+        sin = ops.timestep_embedding(t_dev, _step_dev, self._buf("sin", (B, D), torch.float32), flip=True, shift=0.0, step_error=_step_err)
         sinb = ops.f32_to_bf16(tap("sin", sin), self._buf("sinb", (B, D)))
         th = ops.gemm(tap("sinb", sinb), w["t1"], self._buf("th", (B, D)), act=ops.ACT_SILU)
         ops.gemm(tap("th", th), w["t2"], self._token(tokens, 3), residual=w["pos"][3:4], res_mod=1)
@@ -330,19 +332,21 @@ class Stage1_PriorPipeline:
             st = dict(key=key, x=torch.empty_like(x), emb=torch.empty_like(emb), sp=torch.empty_like(sp), tp=torch.empty_like(tp),
                       ts=torch.empty(n, dtype=torch.int64, device=dev), coef=torch.empty(n, 8, dtype=torch.float32, device=dev),
                       noise=torch.empty(n, x.numel(), dtype=torch.float32, device=dev),
-                      step=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
+                      step=torch.zeros(1, dtype=torch.int32, device=dev),
+                      step_err=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
             self._gst = st
         st["x"].copy_(x); st["emb"].copy_(emb); st["sp"].copy_(sp); st["tp"].copy_(tp)
         st["ts"].copy_(torch.tensor(ts, dtype=torch.int64))
         st["coef"].copy_(torch.tensor(rows, dtype=torch.float32))
         st["noise"].copy_(torch.stack([z.reshape(-1) for z in noises]))
         st["step"].zero_()
+        st["step_err"].zero_()
 
         def step():
             xin = torch.cat([st["x"], st["x"]]) if cfg_on else st["x"]
             pred = prior(xin.unsqueeze(1), timestep=st["ts"], proj_embedding=st["emb"], encoder_hidden_states=st["sp"],
-                         encoder_hidden_states1=st["tp"], attention_mask=None, _step_dev=st["step"]).predicted_image_embedding
-            ops.unclip_step_dev(pred, cfg_on, g, st["x"], st["noise"], st["coef"], st["step"])
+                         encoder_hidden_states1=st["tp"], attention_mask=None, _step_dev=st["step"], _step_err=st["step_err"]).predicted_image_embedding
+            ops.unclip_step_dev(pred, cfg_on, g, st["x"], st["noise"], st["coef"], st["step"], st["step_err"])
             ops.advance_step(st["step"])
         # the step-invariant tokens (poses, image embedding) are refreshed eagerly from this call's tensors; the captured step then
         # finds them cached (same static tensors, same versions) and contains only the per-step kernels
@@ -363,7 +367,17 @@ class Stage1_PriorPipeline:
             step_tokens(prior._buf("tokens", (B * prior.num_tokens, prior.inner_dim)), st["emb"], st["sp"], st["tp"], B)
         for _ in range(n):
             st["graph"].replay()
-        return st["x"].clone()
+        out = st["x"].clone()
+        self._check_step_counter()
+        return out
+
+    def _check_step_counter(self):
+        """Raise if a replay of the captured step found the device step counter outside the timestep / coefficient / noise tables of this call
+        (the kernels clamp such a counter into the tables and raise the flag): one 4-byte read behind the loop."""
+        st = getattr(self, "_gst", None)
+        if st is not None and int(st["step_err"].item()) != 0:
+            raise RuntimeError("the device step counter left the step tables of this sampling call (clamped on the device): "
+                               "the captured step was replayed more often than the schedule has steps")
 
     def get_zero_embed(self, batch_size=1, device=None):
         if self.image_encoder is None:

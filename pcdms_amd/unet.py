@@ -576,8 +576,10 @@ class Stage2_InapintUNet2DConditionModel(HipModel):
             temb = cond.temb_all[0]
             rv_step, rv_stride, rv_count, rv_err = step_dev, cond.temb_all.stride(0), cond.temb_all.shape[0], cond.step_error
         else:
+            # (no prepared table for this t_dev: the counter is bounded into the t_dev.numel() rows this call was given -- a caller who passes
+            # a view shorter than the buffer behind it keeps the contract counter < length himself, include/pcdm.h)
             t_emb = ops.timestep_embedding(t_dev, step_dev, self._buf("t_emb", (B, boc[0]), torch.float32),
-                                           cfg.flip_sin_to_cos, float(cfg.freq_shift))
+                                           cfg.flip_sin_to_cos, float(cfg.freq_shift), step_error=cond.step_error)
             e1 = ops.small_linear(t_emb, W["time1"][0], W["time1"][1], self._buf("e1", (B, temb_dim), torch.float32), act_out=True)
             # emb = time_emb + class_emb is only ever consumed as silu(emb) (ResnetBlock2D): apply it here, once
             emb_act = ops.small_linear(e1, W["time2"][0], W["time2"][1], self._buf("emb", (B, temb_dim), torch.float32),

@@ -60,7 +60,8 @@ def test_missing_library_fails_loudly(tmp_path):
 def test_struct_layouts_match_the_header(tmp_path):
     """The ctypes mirrors in pcdms_amd/_lib.py against the C structs of include/pcdm.h as gcc lays them out: size and the offset of every
     field (pcdm_gemm_params grew without a version bump -- an ABI drift between the header and a binding must fail a test, and
-    ``pcdm_version()`` must say 5 for the struct that starts with ``struct_size`` and ends with ``a3``, ``lda3``)."""
+    ``pcdm_version()`` must say 6 for the header whose ``pcdm_gn_splitk_src`` starts with ``struct_size`` and whose step-indexed table readers
+    take ``rows`` / ``step_error``)."""
     import shutil
     import subprocess
 
@@ -87,10 +88,13 @@ def test_struct_layouts_match_the_header(tmp_path):
             assert int(got[f"{cname}.{fname}"]) == getattr(ct, fname).offset, (cname, fname)
     # every field of the header's struct is mirrored (a field added to the header only would shift nothing above but be left unset)
     hdr = (ROOT / "include" / "pcdm.h").read_text()
-    body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct pcdm_gemm_params {"):hdr.index("} pcdm_gemm_params;")], flags=re.S)
-    names = re.findall(r"(\w+)\s*(?:,|;)", body.split("{", 1)[1])
-    assert names == [f for f, _ in _lib.GemmParams._fields_], (names, [f for f, _ in _lib.GemmParams._fields_])
-    assert ctypes.CDLL(str(build_lib())).pcdm_version() == 5
+    for cname, ct in (("pcdm_gemm_params", _lib.GemmParams), ("pcdm_gn_splitk_src", _lib.GnSplitKSrc)):
+        body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct %s {" % cname):hdr.index("} %s;" % cname)], flags=re.S)
+        names = re.findall(r"(\w+)\s*(?:,|;)", body.split("{", 1)[1])
+        assert names == [f for f, _ in ct._fields_], (cname, names, [f for f, _ in ct._fields_])
+    assert _lib.GnSplitKSrc.struct_size.offset == 0 and _lib.GnSplitKSrc().struct_size == ctypes.sizeof(_lib.GnSplitKSrc) == int(got["pcdm_gn_splitk_src"])
+    assert ctypes.CDLL(str(build_lib())).pcdm_version() == 6
+    assert re.search(r"#define PCDM_ABI_VERSION 6\b", hdr)
 
 
 def test_gemm_params_of_another_size_are_refused(monkeypatch):

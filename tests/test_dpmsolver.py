@@ -274,8 +274,8 @@ def test_dpmpp_step_kernel(backend, cfg, with_noise):
     backend.sync()
     assert _rel(xd, want) <= 1e-6 and _rel(m1d, m0) <= 1e-6                     # x and the history slot updated in place
     from pcdms_amd import _lib
-    assert _lib.lib().pcdm_dpmpp_step(eps.data_ptr(), 0, 1.0, xd.data_ptr(), m1d.data_ptr(), None, None, None, n, None) == -1
-    assert _lib.lib().pcdm_dpmpp_step(eps.data_ptr(), 0, 1.0, xd.data_ptr(), m1d.data_ptr(), None, coef.data_ptr(), None, 0, None) == -1
+    assert _lib.lib().pcdm_dpmpp_step(eps.data_ptr(), 0, 1.0, xd.data_ptr(), m1d.data_ptr(), None, None, steps, None, None, n, None) == -1
+    assert _lib.lib().pcdm_dpmpp_step(eps.data_ptr(), 0, 1.0, xd.data_ptr(), m1d.data_ptr(), None, coef.data_ptr(), steps, None, None, 0, None) == -1
 
 
 @pytest.mark.parametrize("variant", ["2m", "2m_heun_karras", "sde", "sde_heun_karras"])

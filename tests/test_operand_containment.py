@@ -491,7 +491,9 @@ def case_small_linear(P):
 def case_timestep_embedding(P):
     out = []
     for t in (torch.tensor([801, 401, 1], dtype=I64), torch.tensor([801.0, 400.25, 1.0])):
-        out.append(ops.timestep_embedding(P(t), P(torch.tensor([2], dtype=I32), 4), P.out((3, 64), F32)))
+        for step in (2, _beyond(P, 3)):                       # the last row, and a counter beyond the table (clamped to it: the flag is an output)
+            err = P(Z(1, dtype=I32), 4)
+            out += [ops.timestep_embedding(P(t), P(torch.tensor([step], dtype=I32), 4), P.out((3, 64), F32), step_error=err), err]
         out.append(ops.timestep_embedding(P(t[:1]), None, P.out((1, 6), F32), flip=False, shift=1.0))
         out.append(ops.timestep_embedding_rows(P(t), P.out((3, 64), F32)))
         out.append(ops.timestep_embedding_rows(P(t), P.out((3, 6), F32), flip=False))
@@ -534,17 +536,29 @@ def _state(P, n, k, seed=0):
     return [P(rn(seed + i, n)) for i in range(k)]
 
 
+def _beyond(P, rows):
+    """a step counter beyond a table of ``rows`` rows.  Guard pages (CPU): 9 with 3 rows.  Fills (GPU): ``rows`` -- the first row behind the
+    table, which even an unbounded read finds inside the window's 4 KiB margin while a row is at most that long (asserted by the callers'
+    shapes: the widest row here is 260 floats)"""
+    assert rows == 3 and G.WindowPlace.MARGIN >= 260 * 4
+    return rows if P.device.type == "cuda" else 9
+
+
 @case("steps", "pcdm_cfg_step")
 def case_cfg_step(P):
     out = []
-    for n in (1, 63):
-        coef, st = P(rn(9, 3, 4)), P(torch.tensor([2], dtype=I32), 4)
-        xp, eo = P.out((n,), F32), P.out((n,), F32)
-        ops.cfg_step(P(rn(1, 2 * n)), True, 7.5, P(rn(2, n)), xp, coef, st, noise=P(rn(3, n)), eps_out=eo)
-        out += [xp, eo]
+    for n in (1, 63, 260):
+        for step in (2, _beyond(P, 3)):                       # the last row, and a counter beyond the table
+            coef, st, err = P(rn(9, 3, 4)), P(torch.tensor([step], dtype=I32), 4), P(Z(1, dtype=I32), 4)
+            xp, eo = P.out((n,), F32), P.out((n,), F32)
+            ops.cfg_step(P(rn(1, 2 * n)), True, 7.5, P(rn(2, n)), xp, coef, st, noise=P(rn(3, n)), eps_out=eo, step_error=err)
+            out += [xp, eo, err]
         xp = P.out((n,), F32)
-        ops.cfg_step(P(rn(1, n)), False, 1.0, P(rn(2, n)), xp, coef, None)
+        ops.cfg_step(P(rn(1, n)), False, 1.0, P(rn(2, n)), xp, P(rn(9, 3, 4)), None)
         out.append(xp)
+        eo = P.out((n,), F32)                                 # the CFG combine alone: no table
+        ops.cfg_step(P(rn(1, 2 * n)), True, 7.5, None, None, None, eps_out=eo)
+        out.append(eo)
     return out
 
 
@@ -567,15 +581,16 @@ def case_multistep_step(P):
 def case_unipc_dpmpp_step(P):
     out = []
     for n in (1, 63, 260):
-        for cfg in (True, False):
+        for cfg, step in ((True, 2), (False, None), (True, _beyond(P, 3))):     # the last row, no counter, a counter beyond the tables
             st = _state(P, n, 4, seed=n)
             c12 = rn(9, 3, 12)
             c12[:, 2] = 1.0
-            ops.unipc_step(P(rn(1, (2 if cfg else 1) * n)), cfg, 2.0, *st, P(c12), P(torch.tensor([2], dtype=I32), 4))
+            e1, e2 = P(Z(1, dtype=I32), 4), P(Z(1, dtype=I32), 4)
+            ops.unipc_step(P(rn(1, (2 if cfg else 1) * n)), cfg, 2.0, *st, P(c12), P(torch.tensor([2 if step is None else step], dtype=I32), 4), e1)
             s2 = _state(P, n, 2, seed=n + 7)
             ops.dpmpp_step(P(rn(1, (2 if cfg else 1) * n)), cfg, 2.0, *s2, P(rn(8, 3, n)) if cfg else None, P(rn(10, 3, 8)),
-                           P(torch.tensor([2], dtype=I32), 4) if cfg else None)
-            out += st + s2
+                           None if step is None else P(torch.tensor([step], dtype=I32), 4), e2)
+            out += st + s2 + [e1, e2]
     return out
 
 
@@ -586,10 +601,11 @@ def case_unclip_step(P):
     for n in (1, 63, 260):
         for cfg in (True, False):
             out.append(ops.unclip_step(P(rn(1, (2 if cfg else 1) * n)), cfg, 4.0, P(rn(2, n)), P(rn(3, n)) if cfg else None, P.out((n,), F32), c8))
-            x = P(rn(2, n))
-            ops.unclip_step_dev(P(rn(1, (2 if cfg else 1) * n)), cfg, 4.0, x, P(rn(8, 3, n)) if cfg else None, P(torch.tensor([c8] * 3)),
-                                P(torch.tensor([2], dtype=I32), 4))
-            out.append(x)
+            for step in (2, _beyond(P, 3)):                   # the last row, and a counter beyond the tables
+                x, err = P(rn(2, n)), P(Z(1, dtype=I32), 4)
+                ops.unclip_step_dev(P(rn(1, (2 if cfg else 1) * n)), cfg, 4.0, x, P(rn(8, 3, n)) if cfg else None, P(torch.tensor([c8] * 3)),
+                                    P(torch.tensor([step], dtype=I32), 4), err)
+                out += [x, err]
     return out
 
 
@@ -1265,14 +1281,16 @@ def _z(*shape, dtype=F32):
 def _wrapper_calls():
     n, I = 6, I32
     return {
-        "cfg_step": (lambda eps, x, noise, x_prev, eps_out, coef, step: ops.cfg_step(eps, True, 2.0, x, x_prev, coef, step, noise=noise, eps_out=eps_out),
-                     dict(eps=_z(2 * n), x=_z(n), noise=_z(n), x_prev=_z(n), eps_out=_z(n), coef=_z(3, 4), step=_z(2, dtype=I))),
+        "cfg_step": (lambda eps, x, noise, x_prev, eps_out, coef, step, err: ops.cfg_step(eps, True, 2.0, x, x_prev, coef, step, noise=noise, eps_out=eps_out,
+                                                                                          step_error=err),
+                     dict(eps=_z(2 * n), x=_z(n), noise=_z(n), x_prev=_z(n), eps_out=_z(n), coef=_z(3, 4), step=_z(2, dtype=I), err=_z(2, dtype=I))),
         "small_linear": (lambda x, w, bias, add, out: ops.small_linear(x, w, bias, out, add=add),
                          dict(x=_z(3, 8), w=_z(5, 8, dtype=BF16), bias=_z(5), add=_z(3, 5), out=_z(3, 5))),
         "nhwc_bf16_to_nchw": (lambda x: ops.nhwc_bf16_to_nchw(x, 2, 8, 3, 5), dict(x=_z(2, 15, 8, dtype=BF16))),
         "nchw_to_nhwc_bf16": (lambda out: ops.nchw_to_nhwc_bf16(_z(2, 3, 3, 5), out), dict(out=_z(2, 3, 5, 8, dtype=BF16))),   # (x is converted)
         "f32_to_bf16": (lambda x, out: ops.f32_to_bf16(x, out), dict(x=_z(n), out=_z(n, dtype=BF16))),
-        "timestep_embedding": (lambda t, step, out: ops.timestep_embedding(t, step, out), dict(t=_z(3, dtype=I64), step=_z(2, dtype=I), out=_z(2, 64))),
+        "timestep_embedding": (lambda t, step, out, err: ops.timestep_embedding(t, step, out, step_error=err),
+                               dict(t=_z(3, dtype=I64), step=_z(2, dtype=I), out=_z(2, 64), err=_z(2, dtype=I))),
         "timestep_embedding_rows": (lambda t, out: ops.timestep_embedding_rows(t, out), dict(t=_z(3, dtype=I64), out=_z(3, 64))),
         "time_class_combine": (lambda e, c, out: ops.time_class_combine(e, c, out, 2), dict(e=_z(3, 8), c=_z(2, 8), out=_z(6, 8, dtype=BF16))),
         "advance_step": (lambda step: ops.advance_step(step), dict(step=_z(2, dtype=I))),
@@ -1282,17 +1300,17 @@ def _wrapper_calls():
         "layernorm": (lambda x, g, b, out: ops.layernorm(x, g, b, 1e-5, out), dict(x=_z(3, 72, dtype=BF16), g=_z(72), b=_z(72), out=_z(3, 72, dtype=BF16))),
         "groupnorm": (lambda x1, x2, g, b, out: ops.groupnorm(x1, x2, 2, 5, 8, 1e-5, g, b, True, out, _z(8)),   # (ws: sized by a query the stub answers 0)
                       dict(x1=_z(10, 32, dtype=BF16), x2=_z(10, 32, dtype=BF16), g=_z(64), b=_z(64), out=_z(10, 64, dtype=BF16))),
-        "unipc_step": (lambda eps, x, m1, m2, last, coef, step: ops.unipc_step(eps, True, 2.0, x, m1, m2, last, coef, step),
-                       dict(eps=_z(2 * n), x=_z(n), m1=_z(n), m2=_z(n), last=_z(n), coef=_z(3, 12), step=_z(2, dtype=I))),
-        "dpmpp_step": (lambda eps, x, m1, noise, coef, step: ops.dpmpp_step(eps, True, 2.0, x, m1, noise, coef, step),
-                       dict(eps=_z(2 * n), x=_z(n), m1=_z(n), noise=_z(3, n), coef=_z(3, 8), step=_z(2, dtype=I))),
+        "unipc_step": (lambda eps, x, m1, m2, last, coef, step, err: ops.unipc_step(eps, True, 2.0, x, m1, m2, last, coef, step, err),
+                       dict(eps=_z(2 * n), x=_z(n), m1=_z(n), m2=_z(n), last=_z(n), coef=_z(3, 12), step=_z(2, dtype=I), err=_z(2, dtype=I))),
+        "dpmpp_step": (lambda eps, x, m1, noise, coef, step, err: ops.dpmpp_step(eps, True, 2.0, x, m1, noise, coef, step, err),
+                       dict(eps=_z(2 * n), x=_z(n), m1=_z(n), noise=_z(3, n), coef=_z(3, 8), step=_z(2, dtype=I), err=_z(2, dtype=I))),
         "multistep_step": (lambda eps, x, xs, h1, h2, h3, noise, coef, step, err: ops.multistep_step(eps, True, 2.0, x, xs, h1, h2, h3, noise, coef, step, err),
                            dict(eps=_z(2 * n), x=_z(n), xs=_z(n), h1=_z(n), h2=_z(n), h3=_z(n), noise=_z(3, n), coef=_z(3, 12), step=_z(2, dtype=I),
                                 err=_z(2, dtype=I))),
         "unclip_step": (lambda pred, x, noise, out: ops.unclip_step(pred, True, 2.0, x, noise, out, (1.0,) * 8),
                         dict(pred=_z(2 * n), x=_z(n), noise=_z(n), out=_z(n))),
-        "unclip_step_dev": (lambda pred, x, noise, coef, step: ops.unclip_step_dev(pred, True, 2.0, x, noise, coef, step),
-                            dict(pred=_z(2 * n), x=_z(n), noise=_z(3, n), coef=_z(3, 8), step=_z(2, dtype=I))),
+        "unclip_step_dev": (lambda pred, x, noise, coef, step, err: ops.unclip_step_dev(pred, True, 2.0, x, noise, coef, step, err),
+                            dict(pred=_z(2 * n), x=_z(n), noise=_z(3, n), coef=_z(3, 8), step=_z(2, dtype=I), err=_z(2, dtype=I))),
         "assemble_input": (lambda lat, mask, masked, out: ops.assemble_input(lat, 2, mask, masked, out),
                            dict(lat=_z(2, 4, 3, 5), mask=_z(4, 1, 3, 5), masked=_z(4, 4, 3, 5), out=_z(4, 3, 5, 16, dtype=BF16))),
         "assemble_input_ex": (lambda lat, mask, masked, out, tab, step, err: ops.assemble_input_ex(lat, 2, mask, masked, out, tab, 7, step, err),
@@ -1340,6 +1358,27 @@ def test_wrapper_refuses_before_the_library_is_called(stub, name):
             with pytest.raises((AssertionError, ValueError, RuntimeError, TypeError, IndexError)):
                 call(**bad)
             assert not stub.calls, f"ops.{name}: operand '{key}' ({kind}) reached the library ({stub.calls})"
+
+
+@pytest.mark.parametrize("name", ("cfg_step", "unipc_step", "dpmpp_step", "unclip_step_dev"))
+def test_wrapper_refuses_a_step_table_of_another_shape(stub, name):
+    """the row count the library bounds the counter with is ``coef.shape[0]``: a 1-D coef (no row count), a coef of another row width, a coef one
+    row short of noise_all and a step_error of the wrong dtype are refused before the library is called"""
+    call, operands = _wrapper_calls()[name]
+    call(**operands)
+    assert stub.calls
+    coef = operands["coef"]
+    bad = [("a 1-D coef", dict(coef=coef.reshape(-1))), ("a coef of another row width", dict(coef=_z(3, coef.shape[1] + 4))),
+           ("a step_error of the wrong dtype", dict(err=_z(2, dtype=I64))), ("a float step_error", dict(err=_z(2)))]
+    if "noise" in operands and operands["noise"].dim() == 2:
+        bad.append(("coef one row short of noise_all", dict(coef=coef[:-1].contiguous())))
+        bad.append(("noise_all one row short of coef", dict(noise=operands["noise"][:-1].contiguous())))
+        bad.append(("a flat noise_all", dict(noise=operands["noise"].reshape(-1))))
+    for what, change in bad:
+        del stub.calls[:]
+        with pytest.raises(AssertionError):
+            call(**dict(operands, **change))
+        assert not stub.calls, f"ops.{name}: {what} reached the library"
 
 
 def test_wrapper_check_removed_reaches_the_stub(stub, monkeypatch):

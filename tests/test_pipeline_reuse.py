@@ -27,9 +27,9 @@ Row 9: ``DDIMScheduler`` refuses ``prediction_type="v_prediction"`` at construct
 scheduler object of the same class and ``kind`` with other coefficients) with ``timestep_spacing="trailing"``.
 
 Step overflow: a callback of the step BEFORE the last pushes the device step counter past the tables, so exactly one step runs there (after
-the last step no kernel reads a table any more).  ``pcdm_cfg_step`` (DDIM) does not bound its coefficient row -- only the UNet's time table
-and the table-step samplers' kernels clamp -- so the test gives ``st["coef"]`` zeroed slack rows: every read of the test stays
-inside the tensor.
+the last step no kernel reads a table any more).  Every reader of a step-indexed table bounds the counter on the device (include/pcdm.h, ABI 6;
+tests/test_step_counter.py holds each of them to it on guarded and windowed tables first), so the test runs on the pipeline's own ``[n, width]``
+coefficient table and ``[n, numel]`` noise table, for every sampler kind; the stage-1 prior's captured step is replayed once too often likewise.
 """
 from __future__ import annotations
 
@@ -555,30 +555,81 @@ def test_context_at_two_context_lengths(backend):
         ctx.forward(x_in, ts[9], step, B + 1, h, w, 1)                              # nothing prepared at this shape: refused before any launch
 
 
+OVERFLOW_KINDS = {"linear": ("ddim", 4), "unipc": ("unipc", 12), "dpm": ("dpm", 8), "dpm_sde": ("dpm_sde", 8), "table_step": ("euler", 12)}
+
+
 @pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(OVERFLOW_KINDS))
 @pytest.mark.parametrize("c_schedule", [False, True], ids=["py", "c"])
-def test_step_overflow_is_reported_on_both_schedules(gpu_backend, c_schedule):
+def test_step_overflow_is_reported_on_both_schedules(gpu_backend, c_schedule, kind):
     """A callback pushes the device step counter past the tables before the last step: the pipeline raises on the Python schedule AND on the C
-    schedule (whose flag lives in the context's workspace), and the next call on the same pipeline succeeds and equals a fresh one.
-    (Coefficient table with zeroed slack rows: module docstring.)"""
+    schedule (whose flag lives in the context's workspace), for every sampler kind, and the next call on the same pipeline succeeds and equals
+    a fresh one.  The tables are the pipeline's own allocations of exactly n rows: the step that runs with the counter at 2n - 1 is bounded by
+    the kernels (tests/test_step_counter.py)."""
     dev = gpu_backend.device
-    a, b = replace(GPU_BASE, c_schedule=c_schedule, inp="A"), replace(GPU_BASE, c_schedule=c_schedule, inp="B")
+    sched, width = OVERFLOW_KINDS[kind]
+    a, b = replace(GPU_BASE, c_schedule=c_schedule, inp="A", sched=sched), replace(GPU_BASE, c_schedule=c_schedule, inp="B", sched=sched)
     n = a.steps
     _warm(dev, (a, b))                                                           # rule 1
     t0 = len(ops._TUNED)
     wk = _Walker(dev, a)
     pipe = wk.pipe
-    assert torch.equal(_run(pipe, replace(a, use_graph=False), dev), _fresh(a, dev))   # (builds `st`; eager == graph: tests/test_karras_samplers.py)
-    slack = torch.zeros(2 * n, 4, dtype=torch.float32, device=dev)
-    pipe._st["coef"] = slack[:n]                                                 # same shape; rows n .. 2n - 1 exist and are zero
-    assert torch.equal(_run(pipe, a, dev), _fresh(a, dev))                       # captures the graph on the slack table
+    if kind == "linear":
+        assert torch.equal(_run(pipe, replace(a, use_graph=False), dev), _fresh(a, dev))   # (eager == graph: tests/test_karras_samplers.py)
+    assert torch.equal(_run(pipe, a, dev), _fresh(a, dev))                       # captures the graph
+    coef = pipe._st["coef"]
+    assert tuple(coef.shape) == (n, width) and coef.is_contiguous() and coef.untyped_storage().nbytes() == n * width * 4   # production layout: no slack
+    assert pipe._st["noise"] is None or tuple(pipe._st["noise"].shape) == (n, a.shape[0] * 4 * a.shape[1] * a.shape[2])
+    assert int(pipe._st["step_err"].item()) == 0
 
     def push(i, t, lat):
         if i == n - 2:
             pipe._st["step"] += n
     with pytest.raises(RuntimeError, match="step counter left the time-embedding table"):
         _run(pipe, b, dev, callback=push)
-    assert pipe._st["coef"].data_ptr() == slack.data_ptr()
+    assert int(pipe._st["step_err"].item()) == 1                                 # the sampler's own step kernel clamped and said so
+    assert pipe._st["coef"].data_ptr() == coef.data_ptr()
     assert torch.equal(_run(pipe, b, dev), _fresh(b, dev))
     assert torch.equal(_run(pipe, a, dev), _fresh(a, dev))
+    assert len(ops._TUNED) == t0
+
+
+@pytest.mark.gpu
+def test_prior_step_overflow_is_reported(gpu_backend):
+    """Stage 1: after a normal graph call the captured step is replayed once more -- the counter is then n, one past the timestep, coefficient and
+    noise tables.  The kernels clamp it and raise the flag, the check behind the replays raises, and a following normal call succeeds and
+    equals a fresh pipeline's output bit for bit."""
+    from oracle import prior as O
+    from pcdms_amd import Stage1_PriorPipeline, Stage1_PriorTransformer
+    from tests.test_prior import _kwargs as prior_kwargs
+    dev = gpu_backend.device
+    cfg = O.PriorConfig.tiny()
+    N, steps = 2, 3
+    g = torch.Generator().manual_seed(21)
+    inp = dict(s_embed=torch.randn(1, 1, cfg.embedding_dim, generator=g), s_pose=torch.randn(1, cfg.pose_dim, generator=g),
+               t_pose=torch.randn(1, cfg.pose_dim, generator=g), latents=torch.randn(N, cfg.embedding_dim, generator=g),
+               variance_noises=[torch.randn(N, cfg.embedding_dim, generator=g) for _ in range(steps)])
+
+    def make():
+        m = Stage1_PriorTransformer(**prior_kwargs(cfg))
+        m.load_state_dict(O.synth_state_dict(cfg, 1))
+        return Stage1_PriorPipeline(m.to(dev)).to(dev)
+
+    def run(pipe):
+        return pipe(num_images_per_prompt=N, num_inference_steps=steps, guidance_scale=2.5, **inp).image_embeds.clone()
+    run(make())                                                                  # rule 1: the tiles of this call are decided
+    t0 = len(ops._TUNED)
+    want = run(make())
+    pipe = make()
+    assert torch.equal(run(pipe), want)
+    st = pipe._gst
+    assert tuple(st["coef"].shape) == (steps, 8) and tuple(st["noise"].shape) == (steps, N * cfg.embedding_dim) and st["ts"].numel() == steps
+    assert int(st["step"].item()) == steps and int(st["step_err"].item()) == 0
+    pipe._check_step_counter()                                                   # nothing to report yet
+    st["graph"].replay()                                                         # one replay too many: the counter is n
+    torch.cuda.synchronize()
+    assert int(st["step"].item()) == steps + 1 and int(st["step_err"].item()) == 1
+    with pytest.raises(RuntimeError, match="step counter left the step tables"):
+        pipe._check_step_counter()
+    assert torch.equal(run(pipe), want)                                          # the flag is zeroed per call; the result is a fresh pipeline's
     assert len(ops._TUNED) == t0

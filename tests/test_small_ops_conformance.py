@@ -310,7 +310,7 @@ def run_cfg_step(backend, n, cfg, step, with_noise, outs, fails, g=7.5, swap_che
         xp = Win(n, F32, dev) if "x_prev" in outs else None
         eo = Win(n, F32, dev) if "eps_out" in outs else None
         rc = lib().pcdm_cfg_step(eps_d.data_ptr(), int(cfg), g, x_d.data_ptr(), ops._ptr(noise_d), xp.ptr if xp else None, eo.ptr if eo else None,
-                                 tab.data_ptr(), ops._ptr(st), n, ops._stream(eps_d))
+                                 tab.data_ptr(), 4, ops._ptr(st), None, n, ops._stream(eps_d))
         return rc, [w for w in (xp, eo) if w is not None]
 
     rc, wins = launch(backend, go)
@@ -366,8 +366,8 @@ def run_unipc(backend, n, cfg, step, corrector, fails, g=2.0):
 
     def go():
         w = {k: Win(n, F32, dev, init=v) for k, v in st0.items()}
-        rc = lib().pcdm_unipc_step(eps_d.data_ptr(), int(cfg), g, w["x"].ptr, w["m1"].ptr, w["m2"].ptr, w["last"].ptr, tab.data_ptr(), ops._ptr(st),
-                                   n, ops._stream(eps_d))
+        rc = lib().pcdm_unipc_step(eps_d.data_ptr(), int(cfg), g, w["x"].ptr, w["m1"].ptr, w["m2"].ptr, w["last"].ptr, tab.data_ptr(), 4, ops._ptr(st),
+                                   None, n, ops._stream(eps_d))
         return rc, [w[k] for k in ("x", "m1", "m2", "last")]
 
     rc, wins = launch(backend, go)
@@ -420,7 +420,7 @@ def test_unipc_three_chained_steps(backend):
             snaps, rc = [], 0
             for s in range(3):
                 rc |= lib().pcdm_unipc_step(eps[s][1].data_ptr(), 1, g, w["x"].ptr, w["m1"].ptr, w["m2"].ptr, w["last"].ptr, tab.data_ptr(),
-                                            step.ptr, n, ops._stream(tab))
+                                            4, step.ptr, None, n, ops._stream(tab))
                 rc |= lib().pcdm_advance_step(step.ptr, ops._stream(tab))
                 snaps.append({k: Win(n, F32, dev, init=v.t) for k, v in w.items()})
             go.snaps, go.step = snaps, step
@@ -475,7 +475,7 @@ def run_dpmpp(backend, n, cfg, step, with_noise, fails, g=2.0):
 
     def go():
         wx, wm = Win(n, F32, dev, init=x), Win(n, F32, dev, init=m1)
-        rc = lib().pcdm_dpmpp_step(eps_d.data_ptr(), int(cfg), g, wx.ptr, wm.ptr, ops._ptr(nz), tab.data_ptr(), ops._ptr(st), n, ops._stream(eps_d))
+        rc = lib().pcdm_dpmpp_step(eps_d.data_ptr(), int(cfg), g, wx.ptr, wm.ptr, ops._ptr(nz), tab.data_ptr(), 4, ops._ptr(st), None, n, ops._stream(eps_d))
         return rc, [wx, wm]
 
     rc, wins = launch(backend, go)
@@ -532,7 +532,8 @@ def run_unclip(backend, n, cfg, c, with_noise, dev_step, fails, g=4.0, alias=Fal
     def go():
         if dev_step is not None:
             wx = Win(n, F32, dev, init=x)
-            rc = lib().pcdm_unclip_step_dev(eps_d.data_ptr(), int(cfg), g, wx.ptr, ops._ptr(nz), tab.data_ptr(), st.data_ptr(), n, ops._stream(eps_d))
+            rc = lib().pcdm_unclip_step_dev(eps_d.data_ptr(), int(cfg), g, wx.ptr, ops._ptr(nz), tab.data_ptr(), 4, st.data_ptr(), None, n,
+                                              ops._stream(eps_d))
         else:
             wx = Win(n, F32, dev, init=x) if alias else Win(n, F32, dev)
             rc = lib().pcdm_unclip_step(eps_d.data_ptr(), int(cfg), g, wx.ptr if alias else x_d.data_ptr(), ops._ptr(nz), wx.ptr, c8, n,
@@ -950,7 +951,7 @@ def test_timestep_embedding(backend, dim):
 
                     def go():
                         o = Win(B * dim, F32, dev)
-                        return lib().pcdm_timestep_embedding(t_d.data_ptr(), ops._ptr(st), o.ptr, B, dim, flip, shift, ops._stream(t_d)), [o]
+                        return lib().pcdm_timestep_embedding(t_d.data_ptr(), 5, ops._ptr(st), None, o.ptr, B, dim, flip, shift, ops._stream(t_d)), [o]
 
                     rc, wins = launch(backend, go)
                     tag = f"timestep_embedding[t={t} dim={dim} flip={flip} shift={shift} step={'index' if use_step else 'NULL'}]"
@@ -1437,7 +1438,8 @@ def test_timestep_bound_bites():
 
 # ------------------------------------------------------------------------------------------------ return codes of the remaining entries
 def test_refusals(backend):
-    """every ``return -1`` of the entries not covered above: the call is refused and the output keeps its bytes"""
+    """every ``return -1`` of the entries not covered above: the call is refused and the output keeps its bytes (for the step-indexed table
+    readers also rows < 1 and a misaligned step_error; their step_dev may be NULL -- row 0 -- so that is no refusal)"""
     dev = backend.device
     L, st = lib(), None
     f = torch.zeros(4096, dtype=F32, device=dev)
@@ -1451,19 +1453,23 @@ def test_refusals(backend):
     o32, o16, o8 = Win(2048, F32, dev), Win(2048, BF16, dev), Win(2048, U8, dev)
     O, Q, B8 = o32.ptr, o16.ptr, o8.ptr
     calls = {
-        "timestep_embedding": (L.pcdm_timestep_embedding, [T, None, O, 2, 64, 1, 0.0, st], {0: None, 2: None, 3: 0, 4: (0, 63, -2)}),
+        "timestep_embedding": (L.pcdm_timestep_embedding, [T, 8, None, None, O, 2, 64, 1, 0.0, st],
+                               {0: None, 4: None, 5: 0, 6: (0, 63, -2), 1: (0, -1), 3: I + 2}),
         "timestep_embedding_rows": (L.pcdm_timestep_embedding_rows, [T, 2, O, 64, 1, 0.0, st], {0: None, 1: 0, 2: None, 3: (0, 63)}),
         "time_class_combine": (L.pcdm_time_class_combine, [F, F, Q, 2, 2, 8, st], {0: None, 2: None, 3: 0, 4: 0, 5: 0}),
         "assemble_input": (L.pcdm_assemble_input, [F, 2, 2, F, 1, F, 1, Q, 2, 2, 16, st], {0: None, 5: None, 7: None, 1: 0, 2: 0, 10: (8, 20, 0)}),
         "nchw_f32_to_nhwc_bf16": (L.pcdm_nchw_f32_to_nhwc_bf16, [F, Q, 2, 3, 8, 5, st], {0: None, 1: None, 2: (0, -1), 3: (0, -1), 5: (0, -1), 4: (12, 0)}),
         "nhwc_bf16_to_nchw_f32": (L.pcdm_nhwc_bf16_to_nchw_f32, [H, O, 2, 3, 5, st], {0: None, 1: None, 2: (0, -1), 3: (0, -1), 4: (0, -1)}),
         "f32_to_bf16": (L.pcdm_f32_to_bf16, [F, Q, 100, st], {0: None, 1: None, 2: (0, -5)}),
-        "cfg_step": (L.pcdm_cfg_step, [F, 1, 2.0, F, None, O, None, F, None, 100, st], {0: None, 9: (0, -1), 3: None, 7: None}),
-        "unipc_step": (L.pcdm_unipc_step, [F, 1, 2.0, O, O + 1024, O + 2048, O + 3072, F, None, 100, st],
-                       {0: None, 3: None, 4: None, 5: None, 6: None, 7: None, 9: (0, -1)}),
-        "dpmpp_step": (L.pcdm_dpmpp_step, [F, 1, 2.0, O, O + 1024, None, F, None, 100, st], {0: None, 3: None, 4: None, 6: None, 8: (0, -1)}),
+        "cfg_step": (L.pcdm_cfg_step, [F, 1, 2.0, F, None, O, None, F, 4, None, None, 100, st],
+                     {0: None, 11: (0, -1), 3: None, 7: None, 8: (0, -1), 10: I + 2}),
+        "unipc_step": (L.pcdm_unipc_step, [F, 1, 2.0, O, O + 1024, O + 2048, O + 3072, F, 4, None, None, 100, st],
+                       {0: None, 3: None, 4: None, 5: None, 6: None, 7: None, 8: (0, -1), 10: I + 2, 11: (0, -1)}),
+        "dpmpp_step": (L.pcdm_dpmpp_step, [F, 1, 2.0, O, O + 1024, None, F, 4, None, None, 100, st],
+                       {0: None, 3: None, 4: None, 6: None, 7: (0, -1), 9: I + 2, 10: (0, -1)}),
         "unclip_step": (L.pcdm_unclip_step, [F, 1, 2.0, F, None, O, c8, 100, st], {0: None, 3: None, 5: None, 6: None, 7: (0, -1)}),
-        "unclip_step_dev": (L.pcdm_unclip_step_dev, [F, 1, 2.0, O, None, F, I, 100, st], {0: None, 3: None, 5: None, 6: None, 7: (0, -1)}),
+        "unclip_step_dev": (L.pcdm_unclip_step_dev, [F, 1, 2.0, O, None, F, 4, I, None, 100, st],
+                            {0: None, 3: None, 5: None, 6: (0, -1), 8: I + 2, 9: (0, -1)}),
         "lincomb": (L.pcdm_lincomb, [O, 3, ptrs, cs, 100, st], {0: None, 1: (0, 7, -1), 2: None, 3: None, 4: (0, -1)}),
         "rescale_noise_cfg": (L.pcdm_rescale_noise_cfg, [F, F, O, 2, 100, 0.7, st], {0: None, 1: None, 2: None, 3: (0, -1), 4: (1, 0)}),
         "gaussian_sample": (L.pcdm_gaussian_sample, [F, F, O, 2, 4, 5, 1.0, st], {0: None, 2: None, 3: 0, 4: 0, 5: 0}),
